@@ -11,7 +11,15 @@ seeds tseed(ii) from master 58302, bond_cond.f:65-70); the only collective
 is the RCCL all-reduce of the ensemble statistics.  Weak scaling.
 
   python bench.py [--gpus N --steps K --warmup W --L 4096 --p 0.6]
+  python bench.py --full ...            # + baselines, probes, in-flight run
+  python bench.py --dump-outputs DIR    # the last timed step's results as .npy
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the JSON line
+(value, ms_per_step and the live per-kernel timing of the timed steps).
+`--full` adds what takes runs of its own after or beside the timed region:
+the CPU baselines, the per-format kernel probe, the stream-copy ceiling, the
+labeling phases, the in-flight run and the host-order upload cost.
 
 `--gpus N` without a launcher starts the N rank processes itself
 (launch_ranks: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as
@@ -392,6 +400,17 @@ def pmc_traffic(base, L_, kind="bond"):
     return tot, src
 
 
+def dump_outputs(path, r):
+    """--dump-outputs: what the last timed step returned to its caller (the
+    conductances at both electrodes, the CG iteration count, the number of
+    spanning clusters), one float64 array of one element each.  The inputs
+    are a function of the arguments alone (seeds tseed(ii) from --master), so
+    two builds run with the same arguments are compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    for name in ("gtop", "gbot", "iter", "nspan"):
+        np.save(os.path.join(path, name + ".npy"), np.array([r[name]], dtype=np.float64))
+
+
 def launch_ranks(n, argv, stub=False):
     """`bench.py --gpus N` without a launcher: start N rank processes (one per
     GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as torch.distributed.run
@@ -504,6 +523,14 @@ def main():
                          "of before it")
     ap.add_argument("--slabs", type=int, default=1,
                     help="row slabs of each CG solve on this GPU (perc_set_slabs; SURVEY §8(f) 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines, the "
+                         "kernel probe of every operator format, the stream-copy ceiling, the "
+                         "labeling phases, the in-flight run and the host-order upload cost "
+                         "(--no-cpu-baseline, --cpu-cores and --inflight narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (gtop, "
+                         "gbot, iter, nspan) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-worker", nargs=6, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--launch-stub", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-cores", type=int, default=0,
@@ -512,6 +539,8 @@ def main():
     args = ap.parse_args()
     if args.cpu_worker:
         return cpu_worker(args.cpu_worker, args.cpu_iters)
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU, started here (the driver may call bench.py
         # --gpus N directly instead of through torch.distributed.run)
@@ -608,8 +637,8 @@ def main():
     # realisations run: the sample at L (same realisation as the first timed
     # one) and one whole L = 1024 solve as a measured anchor
     anchors = {}
-    if (rank == 0 and world == 1 and not args.no_cpu_baseline and args.kind == "bond" and lat == 0
-            and args.occupancy in ("uniform", "device")):
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.kind == "bond"
+            and lat == 0 and args.occupancy in ("uniform", "device")):
         anchors["sample"] = cpu_anchor_start(L_, p, int(seeds[ii_list[args.warmup]]), args.cpu_iters,
                                              args.occupancy)
         anchors["L1024"] = cpu_anchor_start(1024, p, int(seeds[0]), 0, args.occupancy)
@@ -742,6 +771,8 @@ def main():
     nsolves = int(stats[0])
     nspan = int(stats[3])
     value = nsolves / tmax
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[-1])
 
     fmt_names = {P.FMT_STENCIL: "stencil", P.FMT_STENCIL_TILED: "stencil_tiled",
                  P.FMT_STENCIL_SPLIT: "stencil_split", P.FMT_CSR: "csr"}
@@ -812,7 +843,7 @@ def main():
     probe = {}
     for fname, fcode in (("stencil", P.FMT_STENCIL), ("stencil_tiled", P.FMT_STENCIL_TILED),
                          ("stencil_split", P.FMT_STENCIL_SPLIT),
-                         ("csr", P.FMT_CSR)) if assembled else ():
+                         ("csr", P.FMT_CSR)) if assembled and args.full else ():
         try:
             ctx.set_matrix_format(fcode)
         except Exception:
@@ -824,12 +855,12 @@ def main():
             row[key] = {"ms": round(ms, 5), "gbs": round(nbytes / (ms * 1e-3) / 1e9, 1)}
         probe[fname] = row
     sync_floor = None
-    if minfo.get("kernel") == "resident" and assembled:
+    if args.full and minfo.get("kernel") == "resident" and assembled:
         # two block sums + two tagged-granule all-gathers per iteration on
         # the resident grid, nothing else (k_res_sync_probe)
         sync_floor = round(ctx.bench_kernel(6, 20), 5)
     labeling = None
-    if devocc and rank == 0:
+    if args.full and devocc and rank == 0:
         labeling = labeling_probe(ctx, P, L_, nb, tb, [int(seeds[ii_list[k]]) for k in timed][:4],
                                   args.kind, ts if args.kind != "bond" else 0)
     # realisations in flight (one context and stream each): what a throughput
@@ -838,7 +869,7 @@ def main():
     # other's work.  Reported beside `value` (K = 1), whose per-kernel
     # roofline it would blur.
     in_flight = None
-    if (args.inflight > 1 and K == 1 and world == 1 and devocc and args.kind == "bond"
+    if (args.full and args.inflight > 1 and K == 1 and world == 1 and devocc and args.kind == "bond"
             and minfo.get("kernel") != "resident" and timed):
         K2 = args.inflight
         mode0 = args.march_mode if args.march_mode >= 0 else P.MARCH_DEFAULT
@@ -865,10 +896,12 @@ def main():
                      "cg_iterations_mean": round(float(np.mean([r_["iter"] for r_ in res2])), 1),
                      "note": "the timed realisations again, %d in flight (one context and stream "
                              "each), after the timed region; not `value`" % K2}
-    copy_ms = ctx.bench_kernel(4, 20)
-    copy_bytes = 2 * 8 * (64 << 20)  # 512 MB read + 512 MB written (perc_bench_kernel 4)
-    stream_copy = {"ms": round(copy_ms, 5), "bytes": copy_bytes,
-                   "gbs": round(copy_bytes / (copy_ms * 1e-3) / 1e9, 1)}
+    stream_copy = None
+    if args.full:
+        copy_ms = ctx.bench_kernel(4, 20)
+        copy_bytes = 2 * 8 * (64 << 20)  # 512 MB read + 512 MB written (perc_bench_kernel 4)
+        stream_copy = {"ms": round(copy_ms, 5), "bytes": copy_bytes,
+                       "gbs": round(copy_bytes / (copy_ms * 1e-3) / 1e9, 1)}
 
     out = {
         "metric": "CG SpMV GB/s + conductance solves/sec, L=4096 square lattice at p=0.60",
@@ -904,8 +937,9 @@ def main():
                    "concurrent_per_gpu": K, "slabs": args.slabs},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS,
                      "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4),
-                     "achievable": stream_copy["gbs"],
-                     "frac_of_achievable": round(achieved / stream_copy["gbs"], 4),
+                     **({"achievable": stream_copy["gbs"],
+                         "frac_of_achievable": round(achieved / stream_copy["gbs"], 4)}
+                        if stream_copy else {}),
                      "traffic": traffic, "traffic_source": traffic_src,
                      "avg_launch_ms_rocprof": rp_ms, "rocprof_source": rp_src,
                      "timing_note": "avg_launch_ms: every 64th launch timed live by its own "
@@ -945,9 +979,10 @@ def main():
                          "gbs": round(iter_bytes / (iter_ms * 1e-3) / 1e9, 1) if iter_ms > 0
                          else None},
         "cg_kernels": kern,
-        "kernel_probe": probe,
-        "stream_copy": stream_copy,
     }
+    if args.full:
+        out["kernel_probe"] = probe
+        out["stream_copy"] = stream_copy
     if labeling is not None:
         out["labeling"] = labeling
     if in_flight is not None:
@@ -955,7 +990,8 @@ def main():
     if rank == 0 and world == 1 and args.kind == "bond" and devocc:
         out["pcie_inclusive"] = {"note": "occupancy drawn on the device: no host array crosses "
                                          "PCIe per realisation"}
-    if rank == 0 and world == 1 and args.kind == "bond" and host_orders[args.warmup] is not None:
+    if (args.full and rank == 0 and world == 1 and args.kind == "bond"
+            and host_orders[args.warmup] is not None):
         # the host-array boundary (perc_occupy with a host order) adds one
         # PCIe upload of the order per realisation; timed here outside the
         # metric: host-order occupy + label vs device-order occupy + label
@@ -980,7 +1016,8 @@ def main():
             "value": round(nsolves / (tmax + up_s * nsolves), 5), "unit": "solves/s",
             "note": "host-order boundary: value with one H2D upload of the occupation "
                     "order per realisation (occupy+label host minus device, best of 3)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.kind == "bond" and lat == 0:
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.kind == "bond"
+            and lat == 0):
         log("cpu baseline: waiting for the oracle processes ...")
         try:
             if "sample" in anchors:

@@ -108,7 +108,10 @@ build_nr() {
   cp "$REF/Fortran/$src" "$f"
   for e in "$@"; do sed -i "$e" "$f"; done
   sed -i '/SUBROUTINE sprsin/,$d' "$f"
-  "$FLANG" -O2 "$f" "$TMP/gfrand.o" -L"$PERC_LIB" -lperc -Wl,-rpath,"$PERC_LIB" \
+  # libperc is found relative to the binary, so the tree may be moved after
+  # the build (a PERC_LIB given from outside the tree stays absolute)
+  "$FLANG" -O2 "$f" "$TMP/gfrand.o" -L"$PERC_LIB" -lperc \
+    -Wl,-rpath,'$ORIGIN/../../percolation_amd' -Wl,-rpath,"$PERC_LIB" \
     -L"$GF" -lgfortran -Wl,-rpath,"$GF" -o "$OUT/$name"
 }
 if [ -e "$PERC_LIB/libperc.so" ]; then

@@ -192,7 +192,13 @@ def test_route1_relink_of_the_reference_program():
         pytest.skip("a GPU is present: the relinked reference would solve; run it by hand")
     d = tempfile.mkdtemp()
     try:
-        r = subprocess.run([exe], cwd=d, capture_output=True, text=True, timeout=120)
+        # this tree's libperc, wherever the binary was linked: the run path
+        # written at link time may name a directory that is gone or another
+        # tree's build (LD_LIBRARY_PATH is searched before it)
+        libdir = os.path.join(REPO, "percolation_amd")
+        env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+            [libdir] + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]))
+        r = subprocess.run([exe], cwd=d, capture_output=True, text=True, timeout=120, env=env)
         assert "[perc] linbcg_ failed" in r.stderr and "no HIP device" in r.stderr
     finally:
         shutil.rmtree(d)

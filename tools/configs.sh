@@ -1,13 +1,13 @@
 # BASELINE.json configs 2-5 on one GPU (config 4's per-GPU shape), one call
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}; export OUT; mkdir -p "$OUT"
 run() {  # run NAME TIMEOUT ARGS...
   local name=$1 to=$2
   shift 2
-  echo "== $name: $*" >> gpurun_out/configs.log
-  timeout -k 10 "$to" python bench.py "$@" > "gpurun_out/cfg_$name.log" 2>&1
+  echo "== $name: $*" >> $OUT/configs.log
+  timeout -k 10 "$to" python bench.py --full "$@" > "$OUT/cfg_$name.log" 2>&1
   local rc=$?
-  echo "rc=$rc" >> gpurun_out/configs.log
+  echo "rc=$rc" >> $OUT/configs.log
   [ "$rc" -eq 0 ] || exit "$rc"
 }
 run c2_sq1024_bond_p50 600 --L 1024 --p 0.50 --steps 64 --warmup 1 --no-cpu-baseline

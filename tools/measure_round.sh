@@ -8,11 +8,11 @@
 #   TAG=r6_7 bash tools/measure_round.sh
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 TAG=${TAG:-rX}
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}; export OUT; mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 400 python3 bench.py > "gpurun_out/${TAG}_bench.json" 2> "gpurun_out/${TAG}_bench.err" || exit 1
-rm -rf "gpurun_out/${TAG}_prof"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "gpurun_out/${TAG}_prof" -o run -- \
-  python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --inflight 1 > "gpurun_out/${TAG}_benchprof.json" \
-  2> "gpurun_out/${TAG}_benchprof.err" || exit 1
+timeout -k 10 400 python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || exit 1
+rm -rf "$OUT/${TAG}_prof"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_prof" -o run -- \
+  python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --inflight 1 > "$OUT/${TAG}_benchprof.json" \
+  2> "$OUT/${TAG}_benchprof.err" || exit 1
 TAG="" L=4096 timeout -k 10 600 bash tools/pmc_r2.sh || exit 1

@@ -158,6 +158,24 @@ struct KernelTiming {
   long long spmv_n = 0, update_n = 0, p_n = 0;
 };
 
+// The solver's environment knobs (same-box A/Bs and tests), read afresh at
+// the start of every dev_solve / dev_bench (read_march_knobs, perc_solve.hip)
+// and kept on the context for that call.  A flag is on when its variable
+// starts with '1'.
+struct MarchKnobs {
+  bool rm_pu16 = false;    // PERC_MARCH_RM_PU16: the row-major march P on the u16 codes, not the nibble codes
+  bool edge_step = false;  // PERC_MARCH_EDGE_STEP: B stores its edge pairs per step, not staged in LDS
+  bool nodef = false;      // PERC_MARCH_NODEF: PERC_MARCH_DEF ignored
+  int def = 0;             // PERC_MARCH_DEF=<kDefP | kDefB bits>: deferred reductions (opt-in)
+  bool def_sc1 = false;    // PERC_MARCH_DEF_SC1: the deferred totals' loads past L2
+  bool xafter = false;     // PERC_MARCH_XAFTER: x updated after each B's walk, not at the next B's start
+  bool res_flat = false;   // PERC_RES_FLAT: the resident solve's flat all-gather reductions
+  int time_every = 64;     // PERC_TIME_EVERY=<n>: kernel timing samples every n-th iteration of a
+                           // chunk (read once per process)
+  const char* trace = nullptr;  // PERC_MARCH_TRACE=<csv>: phase probe of the strip-major march
+  int trace_it = 1000;          // PERC_MARCH_TRACE_IT=<k>: its first traced iteration
+};
+
 }  // namespace perc
 
 namespace perc {
@@ -246,6 +264,7 @@ struct perc_ctx {
   hipEvent_t ev[8];
   hipEvent_t ev_next[2] = {nullptr, nullptr};  // klaunch: start/stop of the next CG launch
   perc::KernelTiming timing;
+  perc::MarchKnobs knobs;  // as the current dev_solve / dev_bench read them
 };
 
 namespace perc {

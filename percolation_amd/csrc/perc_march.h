@@ -4,6 +4,7 @@
 // anonymous namespace: each translation unit keeps its own copy of what it
 // launches).
 #pragma once
+#include "perc_bands.h"
 #include "perc_cg.h"
 
 // (each TU launches a subset of these internal-linkage helpers)
@@ -450,9 +451,8 @@ __device__ __forceinline__ bool march_def_epilogue(const CGArgs& a, int kk, cons
   return dn;
 }
 
-constexpr int kMarchW = 128;     // columns per wave strip
-constexpr int kEdgeRows = 64;    // band rows whose edge pairs B can stage in LDS (ES)
-constexpr int kMarchWaves = 4;   // waves (strips) per workgroup
+// (kMarchW columns per wave strip, kMarchWaves strips per workgroup, the
+// edge-staging depths kEdgeRows / kEdgeRowsRm: perc_bands.h)
 // A/B probe builds only: the column-class path in the row-major march too
 // (PERC_MARCH_RM_SQ), optionally held to 4 waves per SIMD (PERC_MARCH_RM_SQ4)
 #if defined(PERC_MARCH_RM_SQ) || defined(PERC_MARCH_RM_SQ4)
@@ -965,8 +965,8 @@ __device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, cons
 // TAG: the epilogue reductions by tagged granules (publish_and_reduce_tagged)
 // DEF: deferred reductions (with TAG, strip-major, fast order; see def_totals)
 // ESR > 0: B's edge pairs staged in LDS (ESR rows per side) and stored
-// after the walk -- bands of <= ESR rows: kEdgeRows strip-major, 16 on the
-// row-major march's 8-row bands (the host picks it, CGArgs::mes)
+// after the walk -- bands of <= ESR rows: kEdgeRows strip-major, kEdgeRowsRm
+// on the row-major march's 8-row bands (the host picks it, CGArgs::mes)
 template <int MODE, bool SM = false, int D = kMarchDepth, int PAUX = 0, bool TR = false,
           bool TAG = false, bool PK = false, bool LIT = false, bool DEF = false, int ESR = 0>
 // (the deferred instantiations are held to 3 waves per SIMD -- 168 VGPRs:
@@ -999,6 +999,7 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
   const int w = __builtin_amdgcn_readfirstlane(lb * kMarchWaves + (threadIdx.x >> 6));
   const int spr = m / kMarchW;
   int band, strip;
+  BandRows rows;
   MGeom g;
   if (a.wslots > 0) {
     // slot-weighted bands (PERC_MARCH_SLOTS).  Workgroups are dealt one per
@@ -1023,16 +1024,14 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
     const int q = v / spr;
     strip = v - q * spr;
     band = q * ns + sl;
-    const int c0 = (int)((long long)q * nrows / Q), hc = (int)((long long)(q + 1) * nrows / Q) - c0;
-    const int* wc = a.wcum[MODE == kMarchB ? 1 : 0];
-    g.r0 = c0 + hc * wc[sl] / wc[ns];
-    g.rend = c0 + hc * wc[sl + 1] / wc[ns];
+    rows = slot_band(nrows, Q, q, ns, sl, a.wcum[MODE == kMarchB ? 1 : 0]);
   } else {
     band = w / spr;
     strip = w - band * spr;
-    g.r0 = band * H;
-    g.rend = min(g.r0 + H, nrows);
+    rows = static_band(nrows, H, band);
   }
+  g.r0 = rows.r0;
+  g.rend = rows.rend;
   const bool active = g.r0 < nrows;  // wave-uniform
   const int c0 = strip * kMarchW;
   g.col = c0 + 2 * lane;
@@ -1308,6 +1307,95 @@ __global__ __launch_bounds__(64 * kMarchWaves) void k_march_epi(CGArgs a) {
   double tb[2], bk;
   def_totals<2>(a.mgran_b, a.mnwg, a.mtag, a.merr, tb, s_red, s_grp, true);
   march_def_epilogue(a, a.kiter, tb, threadIdx.x == 0, bk);
+}
+
+// ---------------------------------------------------------------------------
+// The march variants: k_cg_march's template arguments as a value, and the
+// list of every instantiation libperc compiles -- the only place one is
+// named.  perc_solve.hip builds its lookup table from the list and picks a
+// key per launch (select_march); the row-slab solves launch the q-storing
+// entry alone (march_pq_kernel), so perc_slabs.hip compiles just that one.
+struct MarchKey {
+  int mode;  // kMarchPQ / kMarchP / kMarchB
+  bool sm;   // strip-major layout
+  int d, paux;
+  bool tr, tag, pk, lit, def;
+  int esr;
+};
+using MarchKernel = void (*)(CGArgs);
+struct MarchVariant {
+  MarchKey key;
+  MarchKernel fn;
+};
+#define PERC_MARCH_ROW(...) MarchVariant{MarchKey{__VA_ARGS__}, k_cg_march<__VA_ARGS__>},
+
+// q-storing P+S: row slabs, modes without QFREE, literal order past 2 GB of terms
+#define PERC_MARCH_PQ kMarchPQ, false, 3, 0, false, false, false, false, false, 0
+// tagged strip-major P on the u16 codes: the kernel whose occupancy sizes the
+// bands (march_rows_for, march_geometry)
+#define PERC_MARCH_OCC kMarchP, true, 3, kNT, false, true, false, false, false, 0
+
+// Strip-major rows (the default solve at L <= 4096): 3 rows prefetched,
+// nontemporal last-use loads.  Row-major rows (vectors past the Infinity
+// Cache): kMarchDepth rows, P and B on B's 8-row bands (L = 8192: P 0.314 vs
+// 0.355 ms, r4_8; B's nontemporal r(k) loads 0.300 vs 0.331 ms, r4_3).
+// Columns: MODE, SM, D, PAUX, TR, TAG, PK, LIT, DEF, ESR (k_cg_march's order).
+#define PERC_MARCH_VARIANTS(X) \
+  X(PERC_MARCH_PQ)                                                           /* q-storing P+S */ \
+  X(kMarchP, true, 3, kNT, false, false, false, false, false, 0)             /* strip-major P, u16, ticket reduction */ \
+  X(kMarchP, true, 3, kNT, true, false, false, false, false, 0)              /* strip-major P, u16, ticket reduction, phase probe */ \
+  X(PERC_MARCH_OCC)                                                          /* strip-major P, u16, tagged granules */ \
+  X(kMarchP, true, 3, kNT, true, true, false, false, false, 0)               /* strip-major P, u16, tagged granules, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, false, false, true, false, 0)              /* strip-major P, u16, literal order */ \
+  X(kMarchP, true, 3, kNT, false, true, false, true, false, 0)               /* strip-major P, u16, literal order, solve tagged */ \
+  X(kMarchP, true, 3, kNT, false, true, false, false, true, 0)               /* strip-major P, u16, deferred totals (opt-in) */ \
+  X(kMarchP, true, 3, kNT, true, true, false, false, true, 0)                /* strip-major P, u16, deferred totals, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, false, true, false, false, 0)              /* strip-major P, nibble, ticket reduction */ \
+  X(kMarchP, true, 3, kNT, true, false, true, false, false, 0)               /* strip-major P, nibble, ticket reduction, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, true, true, false, false, 0)               /* strip-major P, nibble, tagged granules: the default P */ \
+  X(kMarchP, true, 3, kNT, true, true, true, false, false, 0)                /* strip-major P, nibble, tagged granules, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, false, true, true, false, 0)               /* strip-major P, nibble, literal order */ \
+  X(kMarchP, true, 3, kNT, false, true, true, true, false, 0)                /* strip-major P, nibble, literal order, solve tagged */ \
+  X(kMarchP, true, 3, kNT, false, true, true, false, true, 0)                /* strip-major P, nibble, deferred totals (opt-in) */ \
+  X(kMarchP, true, 3, kNT, true, true, true, false, true, 0)                 /* strip-major P, nibble, deferred totals, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, false, false, false, 0)             /* strip-major B, u16, ticket reduction */ \
+  X(kMarchB, true, 3, kNT, true, false, false, false, false, 0)              /* strip-major B, u16, ticket reduction, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, true, false, false, false, 0)              /* strip-major B, u16, tagged granules */ \
+  X(kMarchB, true, 3, kNT, true, true, false, false, false, 0)               /* strip-major B, u16, tagged granules, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, false, true, false, 0)              /* strip-major B, u16, literal order */ \
+  X(kMarchB, true, 3, kNT, false, true, false, true, false, 0)               /* strip-major B, u16, literal order, solve tagged */ \
+  X(kMarchB, true, 3, kNT, false, true, false, false, true, 0)               /* strip-major B, u16, deferred totals (opt-in) */ \
+  X(kMarchB, true, 3, kNT, true, true, false, false, true, 0)                /* strip-major B, u16, deferred totals, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, true, false, false, false, kEdgeRows)      /* strip-major B, u16, edge pairs staged in LDS */ \
+  X(kMarchB, true, 3, kNT, true, true, false, false, false, kEdgeRows)       /* strip-major B, u16, staged edge pairs, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, true, false, false, 0)              /* strip-major B, nibble, ticket reduction */ \
+  X(kMarchB, true, 3, kNT, true, false, true, false, false, 0)               /* strip-major B, nibble, ticket reduction, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, false, 0)               /* strip-major B, nibble, tagged granules */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, false, 0)                /* strip-major B, nibble, tagged granules, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, true, true, false, 0)               /* strip-major B, nibble, literal order */ \
+  X(kMarchB, true, 3, kNT, false, true, true, true, false, 0)                /* strip-major B, nibble, literal order, solve tagged */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, true, 0)                /* strip-major B, nibble, deferred totals (opt-in) */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, true, 0)                 /* strip-major B, nibble, deferred totals, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, false, kEdgeRows)       /* strip-major B, nibble, edge pairs staged in LDS: the default B */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, false, kEdgeRows)        /* strip-major B, nibble, staged edge pairs, phase probe */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, false, false, false, 0)    /* row-major P, u16 */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, false, true, false, 0)     /* row-major P, u16, literal order */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, true, false, false, 0)     /* row-major P, nibble (128 VGPRs unspilled at the 4-wave bound): past the cache */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, true, true, false, 0)      /* row-major P, nibble, literal order */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, false, false, false, 0)  /* row-major B, u16 */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, false, true, false, 0)   /* row-major B, u16, literal order */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, false, 0)   /* row-major B, nibble, edge pairs stored per step */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, true, true, false, 0)    /* row-major B, nibble, literal order */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, false, kEdgeRowsRm) /* row-major B, nibble, edge pairs staged in LDS: past the cache */
+
+constexpr bool operator==(const MarchKey& a, const MarchKey& b) {
+  return a.mode == b.mode && a.sm == b.sm && a.d == b.d && a.paux == b.paux && a.tr == b.tr && a.tag == b.tag &&
+         a.pk == b.pk && a.lit == b.lit && a.def == b.def && a.esr == b.esr;
+}
+
+MarchKernel march_pq_kernel() {
+  constexpr MarchVariant v[] = {PERC_MARCH_ROW(PERC_MARCH_PQ)};
+  return v[0].fn;
 }
 
 }  // namespace

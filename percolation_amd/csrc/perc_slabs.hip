@@ -113,7 +113,7 @@ hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, 
     b.glo = s > 0 ? -1 : 0;
     b.ghi = s < K - 1 ? b.rows + 1 : b.rows;
     b.march_h = march_rows_for(h, b.rows);  // as march_geometry picks it for these rows
-    b.march_grid = cdiv(spr * cdiv(b.rows, b.march_h), kMarchWaves);
+    b.march_grid = march_grid_for(spr, b.rows, b.march_h);
     b.b_grid = std::max(1, std::min(2 * cus, cg_grid(b.N)));
     b.init_grid = cg_grid(b.N);
     b.red = std::max({b.march_grid, b.b_grid, b.init_grid});
@@ -192,11 +192,12 @@ hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, 
   int chunk = 8;
   long long launched = 0;
   const int kMaxChunk = 256;
+  const MarchKernel march_pq = march_pq_kernel();
   while (true) {
     for (int j = 0; j < chunk; ++j) {
       for (int s = 0; s < K; ++s) {
         A[s].kiter = (int)(launched + j + 1);
-        k_cg_march<kMarchPQ, false, 3><<<sl[s].march_grid, 64 * kMarchWaves, 0, st>>>(A[s]);
+        march_pq<<<sl[s].march_grid, 64 * kMarchWaves, 0, st>>>(A[s]);
       }
       SLAB_TRY(dbg_sync(st, "k_cg_march (slabs)"));
       k_slab_combine<0><<<1, 64, 0, st>>>(S, K, d.err_hist, d.err_hist_cap);
@@ -318,7 +319,7 @@ static hipError_t dslab_setup(perc_ctx* h, int K, int s, int itol, double tol, i
   b.glo = s > 0 ? -1 : 0;
   b.ghi = s < K - 1 ? b.rows + 1 : b.rows;
   b.march_h = march_rows_for(h, b.rows);
-  b.march_grid = cdiv((m / kMarchW) * cdiv(b.rows, b.march_h), kMarchWaves);
+  b.march_grid = march_grid_for(m / kMarchW, b.rows, b.march_h);
   b.b_grid = std::max(1, std::min(2 * cus, cg_grid(b.N)));
   b.init_grid = cg_grid(b.N);
   b.red = std::max({b.march_grid, b.b_grid, b.init_grid});
@@ -398,6 +399,7 @@ hipError_t dev_dslab_step(perc_ctx* h, int op) {
   const Slab& b = D->b;
   CGArgs& a = D->a;
   const size_t row = sizeof(double) * m;
+  const MarchKernel march_pq = march_pq_kernel();
   auto edges_out = [&]() -> hipError_t {
     if (D->s > 0) HIP_TRY(hipMemcpyAsync(D->buf.edge_lo, b.r + m, row, hipMemcpyDeviceToDevice, st));
     if (D->s < K - 1)
@@ -414,7 +416,7 @@ hipError_t dev_dslab_step(perc_ctx* h, int op) {
       break;
     case PERC_DSLAB_PS:  // (the march's epilogue publishes its q.p partial)
       a.kiter = (int)(++D->k);
-      k_cg_march<kMarchPQ, false, 3><<<b.march_grid, 64 * kMarchWaves, 0, st>>>(a);
+      march_pq<<<b.march_grid, 64 * kMarchWaves, 0, st>>>(a);
       break;
     case PERC_DSLAB_COMBINE_PS:
       if (!D->solo)

@@ -69,70 +69,70 @@ void klaunch(perc_ctx* h, K kern, dim3 g, dim3 b, hipStream_t st, const CGArgs& 
   }
 }
 
-// the strip-major q-free march P or B (the default solve at L <= 4096): 3
-// rows prefetched, nontemporal last-use loads and stores, tagged-granule
-// reductions (a.mgran) or the ticket reduction, phase probe (a.mtrace)
-template <int MODE, bool PK>
-void launch_march_sm2(perc_ctx* h, hipStream_t st, const CGArgs& a) {
-  const int grid = a.wslots > 0 ? h->wm_grid : h->march_grid;
-  if (MODE == kMarchB && a.mes && !a.lit && !a.mdef && a.mgran) {  // edge pairs staged in LDS
-    constexpr int kESR = MODE == kMarchB ? kEdgeRows : 0;
-    if (a.mtrace) klaunch(h, k_cg_march<MODE, true, 3, kNT, true, true, PK, false, false, kESR>, grid,
-                          64 * kMarchWaves, st, a);
-    else klaunch(h, k_cg_march<MODE, true, 3, kNT, false, true, PK, false, false, kESR>, grid,
-                 64 * kMarchWaves, st, a);
-  } else if (a.mdef) {  // deferred reductions (opt-in): the next launch forms the totals
-    if (a.mtrace) klaunch(h, k_cg_march<MODE, true, 3, kNT, true, true, PK, false, true>, grid, 64 * kMarchWaves, st, a);
-    else klaunch(h, k_cg_march<MODE, true, 3, kNT, false, true, PK, false, true>, grid, 64 * kMarchWaves, st, a);
-  } else if (a.lit) {  // the literal dot order: the LIT instantiation (term stores)
-    if (a.mgran) klaunch(h, k_cg_march<MODE, true, 3, kNT, false, true, PK, true>, grid, 64 * kMarchWaves, st, a);
-    else klaunch(h, k_cg_march<MODE, true, 3, kNT, false, false, PK, true>, grid, 64 * kMarchWaves, st, a);
-  } else if (a.mgran) {
-    if (a.mtrace) klaunch(h, k_cg_march<MODE, true, 3, kNT, true, true, PK>, grid, 64 * kMarchWaves, st, a);
-    else klaunch(h, k_cg_march<MODE, true, 3, kNT, false, true, PK>, grid, 64 * kMarchWaves, st, a);
-  } else if (a.mtrace) {
-    klaunch(h, k_cg_march<MODE, true, 3, kNT, true, false, PK>, grid, 64 * kMarchWaves, st, a);
-  } else {
-    klaunch(h, k_cg_march<MODE, true, 3, kNT, false, false, PK>, grid, 64 * kMarchWaves, st, a);
-  }
+// every k_cg_march this library compiles (the list: perc_march.h)
+constexpr MarchVariant kMarchTable[] = {PERC_MARCH_VARIANTS(PERC_MARCH_ROW)};
+constexpr MarchKey kMarchOcc = {PERC_MARCH_OCC};
+
+MarchKernel find_march(const MarchKey& k) {
+  for (const MarchVariant& v : kMarchTable)
+    if (v.key == k) return v.fn;
+  return nullptr;
 }
-template <int MODE>
-void launch_march_sm(perc_ctx* h, hipStream_t st, const CGArgs& a) {
-  if (a.nib) launch_march_sm2<MODE, true>(h, st, a);
-  else launch_march_sm2<MODE, false>(h, st, a);
+
+// CUs of the device, and the workgroups a CU holds of the kernel that sizes
+// the bands (PERC_MARCH_OCC)
+void march_occupancy(const perc_ctx* h, int* cus, int* per_cu) {
+  hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, h->device);
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, find_march(kMarchOcc), 64 * kMarchWaves, 0);
+}
+
+// The march kernel of a launch: mode kMarchP for the P side (P of the q-free
+// march, else the q-storing P+S), kMarchB for the q-free B.
+//  strip-major pair (the default solve at L <= 4096; phase probe: a.mtrace):
+//    staged edges (B, a.mes) > deferred > literal > tagged > trace > plain
+//  row-major pair (vectors past the Infinity Cache): literal and nibble codes
+//    independently (P's nibble codes: a.rm_pnib), B's staged edges without lit
+MarchKey select_march(int mode, const perc_ctx* h, const CGArgs& a) {
+  if (!h->qfree) return MarchKey{PERC_MARCH_PQ};
+  const bool lit = a.lit != nullptr, nib = a.nib != nullptr, tag = a.mgran != nullptr, tr = a.mtrace != nullptr;
+  if (!a.sm) {
+    if (mode == kMarchP) return {kMarchP, false, kMarchDepth, 0, false, false, nib && a.rm_pnib, lit, false, 0};
+    return {kMarchB, false, kMarchDepth, kNT, false, false, nib, lit, false, !lit && nib && a.mes ? kEdgeRowsRm : 0};
+  }
+  const MarchKey k = {mode, true, 3, kNT, false, false, nib, false, false, 0};
+  auto with = [k](bool tr, bool tag, bool lit, bool def, int esr) {
+    MarchKey v = k;
+    v.tr = tr, v.tag = tag, v.lit = lit, v.def = def, v.esr = esr;
+    return v;
+  };
+  if (mode == kMarchB && a.mes && !lit && !a.mdef && tag) return with(tr, true, false, false, kEdgeRows);
+  if (a.mdef) return with(tr, true, false, true, 0);
+  if (lit) return with(false, tag, true, false, 0);
+  return with(tr, tag, false, false, 0);
+}
+
+// launch the selected march kernel on its grid (the slot-weighted bands' or
+// the static split's).  A key the table lacks is a programming error: it is
+// reported, never launched as another variant.
+hipError_t launch_march(perc_ctx* h, int mode, hipStream_t st, const CGArgs& a) {
+  const MarchKey k = select_march(mode, h, a);
+  const MarchKernel fn = find_march(k);
+  if (!fn) {
+    fprintf(stderr, "[perc] march variant {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d} is not compiled\n", k.mode, k.sm, k.d,
+            k.paux, k.tr, k.tag, k.pk, k.lit, k.def, k.esr);
+    return hipErrorInvalidConfiguration;
+  }
+  klaunch(h, fn, k.sm && a.wslots > 0 ? h->wm_grid : h->march_grid, 64 * kMarchWaves, st, a);
+  return hipSuccess;
 }
 
 // S(k), or the fused P(k)+S(k) of the tiled stencil kernel
-void launch_cg_spmv(perc_ctx* h, const CGArgs& a, int G) {
+hipError_t launch_cg_spmv(perc_ctx* h, const CGArgs& a, int G) {
   if (h->fused) {
     const int th = h->tile_h;
     const dim3 G2(h->tile_grid), B2(tile_threads(th));
     hipStream_t st = h->stream;
-    if (h->march) {
-      if (h->qfree && a.sm) launch_march_sm<kMarchP>(h, st, a);
-      // row-major q-free P (vectors past the Infinity Cache) on B's 8-row
-      // bands (march_grid): with the x update out of the walk, L = 8192 P
-      // 0.314 vs 0.355 ms on one round of slot-weighted bands, 0.628 vs
-      // 0.656 ms per solve iteration (profiles/r4_8_l8192_ab.json)
-      // Row-major P on the nibble codes (round 6): the column classes formed
-      // per access and only the open-square path compiled in, 128 VGPRs
-      // without spills at the 4-wave bound (round 5's nibble P spilled:
-      // 0.389 / 0.363 vs 0.330 ms on the u16 codes, profiles/r5_14_*);
-      // a.rm_pnib off (PERC_MARCH_RM_PU16=1, A/Bs): the u16 codes
-      else if (h->qfree && a.lit && a.nib && a.rm_pnib)
-        klaunch(h, k_cg_march<kMarchP, false, kMarchDepth, 0, false, false, true, true>, h->march_grid,
-                64 * kMarchWaves, st, a);
-      else if (h->qfree && a.lit)
-        klaunch(h, k_cg_march<kMarchP, false, kMarchDepth, 0, false, false, false, true>, h->march_grid,
-                64 * kMarchWaves, st, a);
-      else if (h->qfree && a.nib && a.rm_pnib)
-        klaunch(h, k_cg_march<kMarchP, false, kMarchDepth, 0, false, false, true>, h->march_grid, 64 * kMarchWaves,
-                st, a);
-      else if (h->qfree) klaunch(h, k_cg_march<kMarchP>, h->march_grid, 64 * kMarchWaves, st, a);
-      // q-storing P+S (row slabs, the literal dot order, modes without QFREE)
-      else klaunch(h, k_cg_march<kMarchPQ, false, 3>, h->march_grid, 64 * kMarchWaves, st, a);
-      return;
-    }
+    if (h->march) return launch_march(h, kMarchP, st, a);
     if (h->g.scn == 4) {
       if (th == 32) klaunch(h, k_cg_ps<4, true, 32>, G2, B2, st, a);
       else if (th == 16) klaunch(h, k_cg_ps<4, true, 16>, G2, B2, st, a);
@@ -152,29 +152,15 @@ void launch_cg_spmv(perc_ctx* h, const CGArgs& a, int G) {
   }
   else if (h->g.scn == 4) klaunch(h, k_cg_spmv<4>, G, kBlock, h->stream, a);
   else klaunch(h, k_cg_spmv<6>, G, kBlock, h->stream, a);
+  return hipSuccess;
 }
 
 // B(k) (streaming; the fused format walks its chunks in reverse)
-void launch_cg_b(perc_ctx* h, const CGArgs& a, int G) {
+hipError_t launch_cg_b(perc_ctx* h, const CGArgs& a, int G) {
   // fused formats: b_grid (set with the lattice, see dev_build_lattice)
   if (h->fused && h->b_grid > 0) G = h->b_grid;
   if (h->march && h->qfree) {
-    if (a.sm) launch_march_sm<kMarchB>(h, h->stream, a);
-    // row-major B: 8-row bands (march_grid, P's too), nontemporal r(k) loads
-    // (L = 8192: 0.300 vs 0.331 ms, profiles/r4_3_l8192_probe.json)
-    else if (a.lit && a.nib)
-      klaunch(h, k_cg_march<kMarchB, false, kMarchDepth, kNT, false, false, true, true>, h->march_grid,
-              64 * kMarchWaves, h->stream, a);
-    else if (a.lit)
-      klaunch(h, k_cg_march<kMarchB, false, kMarchDepth, kNT, false, false, false, true>, h->march_grid,
-              64 * kMarchWaves, h->stream, a);
-    else if (a.nib && a.mes)  // (edge pairs staged in LDS: 16 rows per side)
-      klaunch(h, k_cg_march<kMarchB, false, kMarchDepth, kNT, false, false, true, false, false, 16>, h->march_grid,
-              64 * kMarchWaves, h->stream, a);
-    else if (a.nib)
-      klaunch(h, k_cg_march<kMarchB, false, kMarchDepth, kNT, false, false, true>, h->march_grid, 64 * kMarchWaves,
-              h->stream, a);
-    else klaunch(h, k_cg_march<kMarchB, false, kMarchDepth, kNT>, h->march_grid, 64 * kMarchWaves, h->stream, a);
+    return launch_march(h, kMarchB, h->stream, a);
   } else if (h->stencil) {
     // x on every row with the march's x-in-B (fused, row-major): XF
     if (a.bx && a.xrows == 0 && !a.sm) klaunch(h, k_cg_b<true, true>, G, kBlock, h->stream, a);
@@ -182,6 +168,7 @@ void launch_cg_b(perc_ctx* h, const CGArgs& a, int G) {
   } else {
     klaunch(h, k_cg_b<false>, G, kBlock, h->stream, a);
   }
+  return hipSuccess;
 }
 
 void launch_spmv(perc_ctx* h, const CGArgs& a, const double* x, double* y) {
@@ -200,8 +187,7 @@ hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
   h->nib_used = false;
-  const char* pu16 = std::getenv("PERC_MARCH_RM_PU16");
-  a.rm_pnib = pu16 && pu16[0] == '1' ? 0 : 1;
+  a.rm_pnib = h->knobs.rm_pu16 ? 0 : 1;
   if (!kMarchRmNib || !h->nib_ok || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) || !h->march || !h->qfree ||
       a.sm)
     return hipSuccess;
@@ -225,8 +211,7 @@ hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
     a.ez = d.ez;
     k_edge_init<<<blocks_for(ne), kBlock, 0, st>>>(a);
     HIP_TRY(dbg_sync(st, "k_edge_init"));
-    const char* es = std::getenv("PERC_MARCH_EDGE_STEP");
-    a.mes = a.T.bh <= 16 && !(es && es[0] == '1') ? 1 : 0;  // (B's bands: march_h rows)
+    a.mes = a.T.bh <= kEdgeRowsRm && !h->knobs.edge_step ? 1 : 0;  // (B's bands: march_h rows)
   }
   h->nib_used = !bad;
   return hipSuccess;
@@ -251,22 +236,18 @@ hipError_t setup_granules(perc_ctx* h, CGArgs& a, int itmax) {
   a.mgran_b = h->d.mgran + region;
   a.merr = &h->d.scal->pad[1];
   ++h->solve_epoch;
-  // deferred reductions (k_cg_march DEF, opt-in: PERC_MARCH_DEF=<kDefP |
-  // kDefB bits>): the fast order's march, one slab, grids of <= kDefGroups
-  // reduction groups.  Measured on the metric (profiles/r6_4_def_ab_*): the
+  // deferred reductions (k_cg_march DEF, opt-in: MarchKnobs::def): the fast
+  // order's march, one slab, grids of <= kDefGroups reduction groups.
+  // Measured on the metric (profiles/r6_4_def_ab_*): the
   // collectors' tails are 1.4 (P) and 2.3 us (B), the totals formed at the
   // next launch's start cost 1.7 (one sum) and 3.7 us (two): 0.1511 ms per
   // iteration with the collectors, 0.1515 / 0.1527 / 0.1523 deferred (P's,
   // B's, both) -- the collectors stay the default
   const int grid = a.wslots > 0 ? h->wm_grid : h->march_grid;
-  const char* nodef = std::getenv("PERC_MARCH_NODEF");
-  const char* defb = std::getenv("PERC_MARCH_DEF");
+  const MarchKnobs& kn = h->knobs;
   a.mnwg = grid;
-  a.mdef = !a.lit && !a.slab && red_groups(grid) <= kDefGroups && !(nodef && nodef[0] == '1') && defb
-               ? (std::atoi(defb) & (kDefP | kDefB))
-               : 0;
-  const char* dsc1 = std::getenv("PERC_MARCH_DEF_SC1");  // (A/B: the totals' loads past L2)
-  a.mdsc1 = dsc1 && dsc1[0] == '1' ? 1 : 0;
+  a.mdef = !a.lit && !a.slab && red_groups(grid) <= kDefGroups && !kn.nodef ? (kn.def & (kDefP | kDefB)) : 0;
+  a.mdsc1 = kn.def_sc1 ? 1 : 0;
   return hipSuccess;
 }
 
@@ -358,8 +339,7 @@ hipError_t dev_build_lattice(perc_ctx* h) {
   h->tile_grid = cdiv(std::max(g.n - 2, 0), h->tile_h) * cdiv(g.m, kTileW);
   // register-march kernel (full 128-column strips): reduction buffers for
   // its largest grid (band height 1)
-  h->march_grid_max =
-      g.m % kMarchW == 0 && g.n > 2 ? cdiv((g.m / kMarchW) * (g.n - 2), kMarchWaves) : 0;
+  h->march_grid_max = g.m % kMarchW == 0 && g.n > 2 ? march_grid_for(g.m / kMarchW, g.n - 2, 1) : 0;
   march_geometry(h);
   res_geometry(h);
   // grid of the streaming B in the fused formats.  Vectors that fit the
@@ -443,9 +423,7 @@ int march_rows_for(const perc_ctx* h, int nrows) {
   if ((size_t)g.m * nrows * sizeof(double) > kLargeVector)
     return (h->march_mode & PERC_MARCH_SLOTS) ? 8 : 16;
   int cus = 0, per_cu = 0;
-  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cg_march<kMarchP, true, 3, kNT, false, true>,
-                                               64 * kMarchWaves, 0);
+  march_occupancy(h, &cus, &per_cu);
   const long long slots = (long long)std::max(cus, 1) * std::max(per_cu, 1) * kMarchWaves;
   const long long bands = std::max(1ll, slots / (g.m / kMarchW));
   return std::max(2, cdiv(nrows, bands));
@@ -473,11 +451,9 @@ void march_geometry(perc_ctx* h) {
   if (g.m % kMarchW != 0 || g.n <= 2) return;
   const int spr = g.m / kMarchW, nrows = g.n - 2;
   h->march_h = march_rows_for(h, nrows);
-  h->march_grid = cdiv(spr * cdiv(nrows, h->march_h), kMarchWaves);
+  h->march_grid = march_grid_for(spr, nrows, h->march_h);
   int cus = 0, per_cu = 0;
-  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cg_march<kMarchP, true, 3, kNT, false, true>,
-                                               64 * kMarchWaves, 0);
+  march_occupancy(h, &cus, &per_cu);
   const long long waves = (long long)cus * kMarchWaves;
   const int(*wts)[kMaxSlotRounds] = h->slot_w_set ? h->slot_w : kSlotW;
   bool ok = cus > 0 && per_cu >= 2 && per_cu <= kMaxSlotRounds && waves % spr == 0 &&
@@ -612,24 +588,12 @@ hipError_t to_strips(perc_ctx* h, CGArgs& a) {
     }
   }
   // B stages its edge pairs in LDS where every band of B holds <= kEdgeRows
-  // rows (the bands as k_cg_march forms them; PERC_MARCH_EDGE_STEP=1: the
-  // per-step stores, same-box A/Bs)
-  {
-    const int nrows = a.T.nrows, spr = a.T.m / kMarchW;
-    int hmax = 0;
-    if (a.wslots > 0) {
-      const int ns = a.wslots, ncu = h->wm_grid / ns, Q = ncu * kMarchWaves / spr;
-      const int* wc = a.wcum[1];
-      for (int q = 0; q < Q; ++q) {
-        const int c0 = (int)((long long)q * nrows / Q), hc = (int)((long long)(q + 1) * nrows / Q) - c0;
-        for (int sl = 0; sl < ns; ++sl) hmax = std::max(hmax, hc * wc[sl + 1] / wc[ns] - hc * wc[sl] / wc[ns]);
-      }
-    } else {
-      hmax = a.T.bh;
-    }
-    const char* es = std::getenv("PERC_MARCH_EDGE_STEP");
-    a.mes = hmax <= kEdgeRows && !(es && es[0] == '1') ? 1 : 0;
-  }
+  // rows (the bands as k_cg_march forms them, perc_bands.h: the staging has
+  // no other bound; MarchKnobs::edge_step: the per-step stores)
+  const int ns = a.wslots;
+  const int hmax =
+      ns > 0 ? tallest_slot_band(a.T.nrows, h->wm_grid / ns * kMarchWaves / (a.T.m / kMarchW), ns, a.wcum[1]) : a.T.bh;
+  a.mes = hmax <= kEdgeRows && !h->knobs.edge_step ? 1 : 0;
   return hipSuccess;
 }
 
@@ -728,9 +692,7 @@ hipError_t dev_solve_resident(perc_ctx* h, const CGArgs& ca, int* iter, double* 
   // the flat instantiation from the host, and so does a context whose grouped
   // launch once found the placement uneven (h->res_uneven, reset with the
   // lattice), instead of paying a cooperative launch that leaves at once
-  const char* flat_env = std::getenv("PERC_RES_FLAT");
-  const bool xg = !(flat_env && flat_env[0] == '1') && a.G % 8 == 0 && a.G / 8 <= kResXcdMax &&
-                  !h->res_uneven;
+  const bool xg = !h->knobs.res_flat && a.G % 8 == 0 && a.G / 8 <= kResXcdMax && !h->res_uneven;
   const void* fn = res_kernel(h->res_MT, sq, h->res_NT, a.lit != nullptr, xg);
   KernelTiming& T = h->timing;
   if (T.enabled) {
@@ -782,10 +744,62 @@ hipError_t dev_solve_resident(perc_ctx* h, const CGArgs& ca, int* iter, double* 
 namespace {
 hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,
                           int* iter, double* err);
+
+// the solver's environment knobs (MarchKnobs, perc_internal.h): every value
+// from the environment as it is now, but time_every, which a process reads once
+MarchKnobs read_march_knobs() {
+  auto num = [](const char* name, int unset) {
+    const char* v = std::getenv(name);
+    return v ? std::atoi(v) : unset;
+  };
+  auto flag = [](const char* name) {
+    const char* v = std::getenv(name);
+    return v && v[0] == '1';
+  };
+  static const int time_every = num("PERC_TIME_EVERY", 0);
+  MarchKnobs k;
+  k.rm_pu16 = flag("PERC_MARCH_RM_PU16");
+  k.edge_step = flag("PERC_MARCH_EDGE_STEP");
+  k.nodef = flag("PERC_MARCH_NODEF");
+  k.def = num("PERC_MARCH_DEF", 0);
+  k.def_sc1 = flag("PERC_MARCH_DEF_SC1");
+  k.xafter = flag("PERC_MARCH_XAFTER");
+  k.res_flat = flag("PERC_RES_FLAT");
+  if (time_every > 0) k.time_every = time_every;  // (else the default)
+  k.trace = std::getenv("PERC_MARCH_TRACE");
+  k.trace_it = num("PERC_MARCH_TRACE_IT", 1000);
+  return k;
 }
+
+// What a march solve needs before its first launch: the layout (strip-major
+// copies, or the row-major march's nibble codes), the tagged granules, how x
+// is carried, and what perc_last_solve reports.  probe: perc_bench_kernel's
+// steady-state launches of the same kernels (no solve: last_flags stays).
+hipError_t prepare_march(perc_ctx* h, CGArgs& a, int itmax, bool probe) {
+  if (h->strips) HIP_TRY(to_strips(h, a));
+  else HIP_TRY(to_nib_rows(h, a));
+  HIP_TRY(setup_granules(h, a, itmax));
+  // x on the electrode-side rows, each iteration's update applied by the
+  // next B at its start (k_cg_march, kXin), the last by k_march_xpend
+  // (MarchKnobs::xafter: the update after each B's walk; the probe times the
+  // production path whatever the knob)
+  a.mxin = a.sm && !a.lit && !a.mdef && !a.slab && a.xrows == h->g.m && !(h->knobs.xafter && !probe) ? 1 : 0;
+  if (probe) {
+    if (a.mdef) a.mdef |= kDefBench;  // the deferred march at a fixed iteration: no stop, no scalars
+    return hipSuccess;
+  }
+  const bool host_fold = a.lit && h->dot_order == PERC_DOT_LITERAL_HOST;
+  h->last_flags = (h->dot_order != PERC_DOT_FAST ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0) |
+                  (h->march && h->qfree ? PERC_RAN_QFREE : 0) | (a.sm ? PERC_RAN_STRIPS : 0) |
+                  (a.nib ? PERC_RAN_NIBBLE : 0) | (a.mgran ? PERC_RAN_TAG : 0) |
+                  (host_fold ? PERC_RAN_HOST_FOLD : 0) | (a.mdef ? PERC_RAN_DEFERRED : 0);
+  return hipSuccess;
+}
+}  // namespace
 
 hipError_t dev_solve(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,
                      int* iter, double* err) {
+  h->knobs = read_march_knobs();
   h->last_kernel = h->last_flags = 0;
   h->last_iter = -1;
   const hipError_t e = dev_solve_impl(h, itol, tol, itmax, x0_zero, full_x, iter, err);
@@ -1156,7 +1170,8 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
     a.lit = d.lit;
   }
   h->last_kernel = h->small ? PERC_RAN_SMALL : (h->resident ? PERC_RAN_RESIDENT : (h->march ? PERC_RAN_MARCH : 0));
-  h->last_flags = (literal ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0);
+  // (the one-kernel solves' flags; the launched kernels': prepare_march)
+  if (h->small || h->resident) h->last_flags = (literal ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0);
   if (h->small) {  // one workgroup runs the whole loop (k_cg_small)
     // (x is kept on every row here: the operator is the CSR one and N small)
     if (ST) {
@@ -1188,21 +1203,10 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
     h->last_kernel = h->march ? PERC_RAN_MARCH : 0;
   }
   if (!(h->march && h->qfree)) a.lit = nullptr;  // (the other kernels store no terms)
-  if (h->strips) HIP_TRY(to_strips(h, a));
-  else HIP_TRY(to_nib_rows(h, a));
-  HIP_TRY(setup_granules(h, a, itmax));
-  // x on the electrode-side rows, each iteration's update applied by the
-  // next B at its start (k_cg_march, kXin), the last by k_march_xpend
-  // (PERC_MARCH_XAFTER=1: the update after each B's walk, same-box A/Bs)
-  const char* xafter = std::getenv("PERC_MARCH_XAFTER");
-  a.mxin = a.sm && !a.lit && !a.mdef && !a.slab && a.xrows == h->g.m && !(xafter && xafter[0] == '1') ? 1 : 0;
+  HIP_TRY(prepare_march(h, a, itmax, false));
   HostFold hf;
-  const bool host_fold = a.lit && h->dot_order == PERC_DOT_LITERAL_HOST;
+  const bool host_fold = (h->last_flags & PERC_RAN_HOST_FOLD) != 0;
   if (host_fold) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hf.t), sizeof(double) * 3 * (size_t)h->N));
-  h->last_flags = (literal ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0) |
-                  (h->march && h->qfree ? PERC_RAN_QFREE : 0) | (a.sm ? PERC_RAN_STRIPS : 0) |
-                  (a.nib ? PERC_RAN_NIBBLE : 0) | (a.mgran ? PERC_RAN_TAG : 0) |
-                  (host_fold ? PERC_RAN_HOST_FOLD : 0) | (a.mdef ? PERC_RAN_DEFERRED : 0);
   // iterate in chunks; the device flag makes surplus launches no-ops
   int chunk = 8;
   CGScalars* hsp = nullptr;
@@ -1223,16 +1227,12 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
   // kernel timing samples every kTimeEvery-th iteration of a chunk: 64 (a
   // timed launch's event packets open a dispatch gap of several us: every
   // 8th iteration timed cost ~1 us per iteration on average,
-  // profiles/r6_43_march_gaps.txt; PERC_TIME_EVERY overrides)
-  static const int kTimeEvery = [] {
-    const char* v = std::getenv("PERC_TIME_EVERY");
-    const int n = v ? std::atoi(v) : 0;
-    return n > 0 ? n : 64;
-  }();
-  // phase probe (PERC_MARCH_TRACE=<csv>): per-wave stamps of the P and B
-  // launches of iterations PERC_MARCH_TRACE_IT (default 1000) .. +3
-  const char* mtpath = getenv("PERC_MARCH_TRACE");
-  const int mt_it = getenv("PERC_MARCH_TRACE_IT") ? atoi(getenv("PERC_MARCH_TRACE_IT")) : 1000;
+  // profiles/r6_43_march_gaps.txt; MarchKnobs::time_every overrides)
+  const int kTimeEvery = h->knobs.time_every;
+  // phase probe (MarchKnobs::trace): per-wave stamps of the P and B launches
+  // of iterations trace_it (default 1000) .. +3
+  const char* mtpath = h->knobs.trace;
+  const int mt_it = h->knobs.trace_it;
   constexpr int kMtN = 4;  // traced iterations
   unsigned long long* mtbuf = nullptr;
   const size_t mtwaves = (size_t)std::max(h->march_grid, h->wm_grid) * kMarchWaves;
@@ -1256,7 +1256,7 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
         HIP_TRY(dbg_sync(st, "k_cg_p"));
       }
       if (tm) h->ev_next[0] = ev[2], h->ev_next[1] = ev[3];
-      launch_cg_spmv(h, a, G);
+      HIP_TRY(launch_cg_spmv(h, a, G));
       HIP_TRY(dbg_sync(st, "k_cg_spmv"));
       if (host_fold) {  // akden in ascending j, then ak (on the host)
         HIP_TRY(host_fold_qp(h, a, hf));
@@ -1266,7 +1266,7 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
       }
       if (tm) h->ev_next[0] = ev[4], h->ev_next[1] = ev[5];
       if (a.mtrace) a.mtrace += 4 * mtwaves;
-      launch_cg_b(h, a, G);
+      HIP_TRY(launch_cg_b(h, a, G));
       a.mtrace = nullptr;
       HIP_TRY(dbg_sync(st, "k_cg_b"));
       h->ev_next[0] = h->ev_next[1] = nullptr;
@@ -1373,6 +1373,7 @@ hipError_t dev_selftest_division(long long n, unsigned long long seed, unsigned 
 }
 
 hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
+  h->knobs = read_march_knobs();
   HIP_TRY(ensure_csr(h));  // the probes run every format
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
@@ -1391,14 +1392,7 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
   a.kiter = 2;
   // the solve's layout and reductions for the CG kernels (the plain SpMV
   // probe stays row-major): strip-major copies, tagged granules
-  if (h->strips && (which == 1 || which == 2 || which == 5)) {
-    HIP_TRY(to_strips(h, a));
-    HIP_TRY(setup_granules(h, a, hs.itmax));
-    if (a.mdef) a.mdef |= kDefBench;  // the deferred march at a fixed iteration: no stop, no scalars
-    a.mxin = !a.mdef && a.xrows == h->g.m ? 1 : 0;  // (the production B's x path)
-  } else if (which == 1 || which == 2 || which == 5) {
-    HIP_TRY(to_nib_rows(h, a));
-  }
+  if (which == 1 || which == 2 || which == 5) HIP_TRY(prepare_march(h, a, hs.itmax, true));
   HIP_TRY(hipMemcpyAsync(d.scal, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(d.tickets, 0, kRedSlots * red_tickets_size(red_grid(h)) * sizeof(unsigned),
                          st));
@@ -1412,14 +1406,17 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
     HIP_TRY(hipMemsetAsync(cp_src, 0, cp_n * sizeof(double), st));
   }
   hipError_t lerr = hipSuccess;
+  auto keep = [&](hipError_t le) {  // the first failed launch
+    if (le != hipSuccess && lerr == hipSuccess) lerr = le;
+  };
   auto launch = [&]() {
     const int G = h->grid;
     if (which == 0) {
       launch_spmv(h, a, d.p0, d.q);
     } else if (which == 1) {
-      launch_cg_spmv(h, a, G);
+      keep(launch_cg_spmv(h, a, G));
     } else if (which == 2) {
-      launch_cg_b(h, a, G);
+      keep(launch_cg_b(h, a, G));
     } else if (which == 3) {
       if (ST) k_cg_p<true><<<G, kBlock, 0, st>>>(a);
       else k_cg_p<false><<<G, kBlock, 0, st>>>(a);
@@ -1436,16 +1433,14 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
       (void)hipMemsetAsync(d.res_reg, 0, 9 * kTicketStride * sizeof(unsigned), st);
       (void)hipMemsetAsync(d.res_xg, 0, kResXgDoubles * sizeof(double), st);
       // a refused grid (CUs taken) must not time an empty stream
-      const hipError_t le = hipLaunchCooperativeKernel((const void*)k_res_sync_probe, dim3(ra.G),
-                                                       dim3(h->res_NT), args, 0, st);
-      if (le != hipSuccess && lerr == hipSuccess) lerr = le;
+      keep(hipLaunchCooperativeKernel((const void*)k_res_sync_probe, dim3(ra.G), dim3(h->res_NT), args, 0, st));
     } else if (which == 5) {  // one whole iteration
       if (!h->fused) {
         if (ST) k_cg_p<true><<<G, kBlock, 0, st>>>(a);
         else k_cg_p<false><<<G, kBlock, 0, st>>>(a);
       }
-      launch_cg_spmv(h, a, G);
-      launch_cg_b(h, a, G);
+      keep(launch_cg_spmv(h, a, G));
+      keep(launch_cg_b(h, a, G));
     } else {
       k_copy<<<cdiv(cp_n / 2, kBlock), kBlock, 0, st>>>(cp_src, cp_dst, (int)cp_n);
     }

@@ -724,6 +724,53 @@ def test_nibble_codes_are_bitwise_the_u16_codes(lat, m, n, pbc, p, strips):
         ctx.set_march_mode(PL.MARCH_DEFAULT)
 
 
+@pytest.mark.parametrize("tol,itmax", [(1e-300, 300), (1e-8, 10 ** 6)], ids=["itmax300", "tol1e-8"])
+@pytest.mark.parametrize("m,n,p,strips,slots,knobs", [
+    (512, 512, 0.6, True, False, ("PERC_MARCH_EDGE_STEP", "PERC_MARCH_XAFTER")),   # static 2-row bands
+    (1024, 1024, 0.55, True, True, ("PERC_MARCH_EDGE_STEP", "PERC_MARCH_XAFTER")),  # slot-weighted bands
+    (512, 512, 0.6, False, False, ("PERC_MARCH_RM_PU16", "PERC_MARCH_EDGE_STEP")),  # the row-major march
+])
+def test_march_knobs_are_bitwise_the_default(m, n, p, strips, slots, knobs, tol, itmax, monkeypatch):
+    """The march's A/B knobs pick another instantiation or another store /
+    update schedule of the same per-row arithmetic and the same reduction
+    trees (PERC_MARCH_EDGE_STEP: B's edge pairs stored per step instead of
+    staged in LDS; PERC_MARCH_XAFTER: x updated after each B's walk instead of
+    at the next B's start; PERC_MARCH_RM_PU16: the row-major P on the u16
+    codes): the whole solve is the default's bitwise, stopped by itmax or by
+    the tolerance.  The knobs are read at each solve."""
+    nb = api.nbonds(0, m, n, 0)
+    order = api.shuffled_ids(nb, 99)
+    mode = PL.MARCH_DEFAULT & ~PL.SOLVE_RESIDENT
+    if not strips:
+        mode &= ~PL.MARCH_STRIPS
+    for k in knobs:
+        monkeypatch.delenv(k, raising=False)
+
+    def solve(ctx):
+        c = ctx.conductance(tol=tol, itmax=itmax, vint=True)
+        c["hist"] = ctx.err_history()
+        ran = ctx.last_solve()
+        assert ran["kernel"] == "march" and ran["strips"] == strips and ran["nibble"], ran
+        return c
+
+    with api.Context(0, m, n, 0) as ctx:
+        ctx.occupy(PL.BOND, bond_order=order, nbonds_=int(p * nb))
+        assert ctx.label()["nspan"] > 0
+        ctx.set_march_mode(mode)
+        ref = solve(ctx)
+        info = ctx.march_info()
+        assert info["kernel"] == "wave" and info["strips"] == strips and info["slots"] == slots, info
+        assert (ref["iter"] == itmax + 1) == (itmax == 300), ref["iter"]
+        for k in knobs:
+            monkeypatch.setenv(k, "1")
+            c = solve(ctx)
+            monkeypatch.delenv(k)
+            assert c["iter"] == ref["iter"] and c["err"] == ref["err"], k
+            assert np.array_equal(c["hist"].view(np.uint64), ref["hist"].view(np.uint64)), k
+            assert c["gtop"] == ref["gtop"] and c["gbot"] == ref["gbot"], k
+            assert np.array_equal(c["vint"].view(np.uint64), ref["vint"].view(np.uint64)), k
+
+
 def test_table_division_is_ieee_division():
     """The solver forms z = r/d as div_tab(r, {d, RN(1/d)}) (one product and
     two fmas); bitwise IEEE division over 2^30 random pairs (a over 600

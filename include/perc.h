@@ -584,6 +584,44 @@ int perc_bondc_realisation(perc_ctx *h, int tbonds, const int *bond_order,
                            int on_device, double Va, double g0, double tol,
                            int itmax, perc_realisation *out);
 
+/* ---- batch of small bond realisations (one workgroup each) ------------ *
+ * The reference's bond_cond ensemble (Fortran/Square/bond_cond.f:123-498)
+ * is ~10^5 independent Kirchhoff solves on lattices of 10 x 10 .. 50 x 50.
+ * perc_batch_bondc runs many of them in one launch: item i is the bond
+ * realisation "the first item_count[i] entries of trial item_trial[i]'s
+ * order" (orders: ntrials rows of nb + 1 entries as perc_shuffle leaves
+ * them; the spill slot 0 takes a position and is no bond), and one
+ * workgroup takes it from occupancy through labeling, the spanning test,
+ * assembly and the linbcg loop to the terminal currents in LDS
+ * (PERC_BOND, PERC_RULE_BOND, PERC_CUR_FORTRAN; itol 1 or 2).  solve = 0
+ * stops after the spanning test (labels only).  The dot order is the
+ * context's (perc_set_dot_order; PERC_DOT_LITERAL_HOST runs as
+ * PERC_DOT_LITERAL): literal results are bitwise perc_conductance's under
+ * PERC_DOT_LITERAL, fast ones use the workgroup's own fixed tree (the same
+ * for an item wherever it stands in the batch).  When several clusters span
+ * (nspan > 1) the reference's lowest-label rule needs the host replay:
+ * the item comes back with fallback = 1, filled by perc_occupy /
+ * perc_label / perc_conductance on the context.  The context's single-
+ * realisation state (occupancy, labeling, assembled system) is therefore
+ * what the last fallback item left; without one it is unchanged.
+ * PERC_EINVAL: itol 3 / 4, a lattice perc_batch_supported refuses (text in
+ * perc_last_error), item_trial outside 0..ntrials-1, item_count outside
+ * 0..nb+1. */
+typedef struct {
+  double gtop, gbot, err;
+  int iter, status;                         /* as perc_cond_result */
+  int nclusters, nspan, span_root, span_sites;
+  int fallback;                             /* 1: several clusters span; run through the single path */
+} perc_batch_item;
+/* host-only: 1 when the batch kernel can run this lattice: n >= 3, the
+   interior system has (n-2)*m <= 8192 rows and the stencil operator exists
+   (every interior row one of the stencil forms, every stencil bond present) */
+int perc_batch_supported(int lattice, int m, int n, int pbc);
+int perc_batch_bondc(perc_ctx *h, int ntrials, const int *orders /* ntrials x (nb+1) */,
+                     int nitems, const int *item_trial, const int *item_count, int solve,
+                     double Va, double g0, double leak, int itol, double tol, int itmax,
+                     perc_batch_item *out);
+
 /* ---- ensemble statistics (bond_cond, config 4) ----------------------- */
 /* Accumulate stats for one pb point: {count, sum G, sum G^2, count spanning,
    sum iter} into acc[5*point..]. */
@@ -611,6 +649,20 @@ int perc_ensemble_ndev(perc_ensemble *e);
    idle.  perc_ensemble_workers returns W. */
 int perc_ensemble_set_workers(perc_ensemble *e, int workers);
 int perc_ensemble_workers(perc_ensemble *e);
+/* Batch path of perc_ensemble_bond_cond (default 0: the per-trial loop):
+   with items > 0 and a lattice perc_batch_supported accepts, each device's
+   trials run in groups of about `items` (trial, grid point) realisations --
+   the orders shuffled on the host (perc_shuffle_seeded), one
+   perc_batch_bondc launch per group for the conductances, bf_c by a
+   bisection whose every step is one label-only launch over the group's
+   trials, perccln by perc_replay_labels -- with the per-trial loop's stop
+   rules, outputs and statistics (accumulated in ascending trial order; the
+   workers setting is not used).  Gtop / Gbot differ from the per-trial
+   loop's only by the association of the fast dot order's sums (bitwise the
+   same under PERC_DOT_LITERAL).  On an unsupported lattice the setting is
+   ignored and perc_ensemble_batch returns 0, else it returns items. */
+int perc_ensemble_set_batch(perc_ensemble *e, int items);
+int perc_ensemble_batch(perc_ensemble *e);
 /* device dev's own context (e.g. for single-trial calls); NULL if out of range */
 perc_ctx *perc_ensemble_ctx(perc_ensemble *e, int dev);
 /* the trials device `dev` of `ndev` runs, 1-based, ascending (ii_out may be

@@ -49,6 +49,12 @@ class CondResult(C.Structure):
                 ("t_solve_ms", C.c_double), ("t_currents_ms", C.c_double)]
 
 
+class BatchItem(C.Structure):
+    _fields_ = [("gtop", C.c_double), ("gbot", C.c_double), ("err", C.c_double),
+                ("iter", C.c_int), ("status", C.c_int), ("nclusters", C.c_int), ("nspan", C.c_int),
+                ("span_root", C.c_int), ("span_sites", C.c_int), ("fallback", C.c_int)]
+
+
 class DslabBufs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("part_out", "part_all", "edge_lo", "edge_hi",
                                           "ghost_lo", "ghost_hi")]
@@ -169,6 +175,11 @@ SIGNATURES = {
     "perc_ensemble_ndev": (C.c_int, [_VP]),
     "perc_ensemble_set_workers": (C.c_int, [_VP, C.c_int]),
     "perc_ensemble_workers": (C.c_int, [_VP]),
+    "perc_ensemble_set_batch": (C.c_int, [_VP, C.c_int]),
+    "perc_ensemble_batch": (C.c_int, [_VP]),
+    "perc_batch_supported": (C.c_int, [C.c_int] * 4),
+    "perc_batch_bondc": (C.c_int, [_VP, C.c_int, _I, C.c_int, _I, _I, C.c_int, C.c_double,
+                                   C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _VP]),
     "perc_ensemble_ctx": (C.c_void_p, [_VP, C.c_int]),
     "perc_ensemble_trials": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP]),
     "perc_ensemble_allreduce": (C.c_int, [_VP, _D, C.c_int]),

@@ -93,6 +93,12 @@ def replay_labels(lattice, m, n, pbc, kind, site_order=None, nsites=0, bond_orde
                 maxcs=int(st[2]), perccln=int(st[3]))
 
 
+def batch_supported(lattice, m, n, pbc=0):
+    """perc_batch_supported (host-only): True when the batch kernel can run
+    this lattice -- n >= 3, (n-2)*m <= 8192 interior rows, stencil operator."""
+    return bool(L.lib().perc_batch_supported(lattice, m, n, pbc))
+
+
 class Context:
     """One libperc context (one lattice on one device)."""
 
@@ -328,6 +334,26 @@ class Context:
         out = np.zeros(2, dtype=np.int64)
         L.check(L.lib().perc_system_size(self.h, out), "perc_system_size")
         return int(out[0]), int(out[1])
+
+    def batch_bondc(self, orders, item_trial, item_count, solve=True, Va=1.0, g0=1.0, leak=LEAK,
+                    itol=2, tol=1e-8, itmax=2500):
+        """perc_batch_bondc: many small bond realisations in one launch, one
+        workgroup each.  orders: (ntrials, nb + 1) shuffled id arrays (one
+        array of nb + 1 for one trial); item i occupies the first
+        item_count[i] entries of trial item_trial[i]'s order.  Returns one
+        dict per item (gtop, gbot, err, iter, status, nclusters, nspan,
+        span_root, span_sites, fallback); solve=False stops after the
+        spanning test.  The dot order is the context's."""
+        o = np.ascontiguousarray(orders, dtype=np.int32).reshape(-1, self.nb + 1)
+        it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
+        ic = np.ascontiguousarray(item_count, dtype=np.int32).reshape(-1)
+        if it.shape != ic.shape:
+            raise ValueError("item_trial and item_count differ in length")
+        out = (L.BatchItem * max(len(it), 1))()
+        L.check(L.lib().perc_batch_bondc(self.h, o.shape[0], o.reshape(-1), len(it), it, ic,
+                                         1 if solve else 0, Va, g0, leak, itol, tol, itmax,
+                                         C.cast(out, C.c_void_p)), "perc_batch_bondc")
+        return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
 
     def bondc_realisation(self, order, tbonds, Va=1.0, g0=1.0, tol=1e-8, itmax=2500,
                           device_ptr=None):
@@ -703,7 +729,7 @@ class Ensemble:
     trials striped ii -> device (ii-1) mod ndev, one RCCL all-reduce of the
     per-grid-point statistics (include/perc.h; Square/bond_cond.f:123-498)."""
 
-    def __init__(self, lattice, m, n, pbc=0, ndev=1, devices=None, workers=1):
+    def __init__(self, lattice, m, n, pbc=0, ndev=1, devices=None, workers=1, batch=0):
         self.lattice, self.m, self.n, self.pbc = lattice, m, n, pbc
         self.nb = nbonds(lattice, m, n, pbc)
         h = C.c_void_p()
@@ -715,11 +741,28 @@ class Ensemble:
         self.workers = 1
         if workers != 1:
             self.set_workers(workers)
+        self.batch = 0
+        if batch:
+            self.set_batch(batch)
+
+    def set_batch(self, items):
+        """about `items` (trial, grid point) realisations per launch of the
+        batch kernel in bond_cond (perc_ensemble_set_batch; 0: the per-trial
+        loop).  self.batch is what is in force: 0 on a lattice the batch
+        kernel does not support (batch_supported)."""
+        L.check(L.lib().perc_ensemble_set_batch(self.h, int(items)), "perc_ensemble_set_batch")
+        self.batch = L.lib().perc_ensemble_batch(self.h)
 
     def set_workers(self, workers):
         """contexts (host threads, streams) per device (perc_ensemble_set_workers)"""
         L.check(L.lib().perc_ensemble_set_workers(self.h, workers), "perc_ensemble_set_workers")
         self.workers = L.lib().perc_ensemble_workers(self.h)
+
+    def set_dot_order(self, order):
+        """perc_set_dot_order on every device's context (one worker per device)"""
+        for d in range(self.ndev):
+            L.check(L.lib().perc_set_dot_order(C.c_void_p(L.lib().perc_ensemble_ctx(self.h, d)), order),
+                    "perc_set_dot_order")
 
     def close(self):
         if self.h:

@@ -1,0 +1,550 @@
+// perc_batch.hip -- k_batch_bondc: one workgroup takes one small bond
+// realisation (PERC_BOND, PERC_RULE_BOND, PERC_CUR_FORTRAN) from occupancy to
+// terminal currents with no host round trip -- occupancy from the trial's
+// rank array, union-find labeling in LDS, the spanning rule of k_span_top,
+// assemble_row, k_cg_small's loop (both dot orders) and k_currents' per-site
+// expression.  Many items per launch: the ensemble's (trial, grid point)
+// pairs side by side instead of a dozen launches and one busy CU each.
+#include <climits>
+
+#include "perc_asm_row.h"
+#include "perc_batch.h"
+
+namespace perc {
+namespace {
+
+struct BatchArgs {
+  Geom g;
+  int N, nb;
+  const int* bond_first;
+  const StencilForms* forms;
+  const int* rank;  // ntrials x nb
+  const int* item_trial;
+  const int* item_count;
+  BatchOut* out;
+  double* iout;  // nitems x 2m
+  int* sflag;
+  int fast, fl, fr, bf_closed;
+  int solve, itol, itmax;
+  double Va, g0, leak, tol;
+  BatchLds L;
+};
+
+// root of x (parents only decrease along a chain; hooks of other threads may
+// land while it is walked: every value read is an ancestor at some moment)
+__device__ __forceinline__ int lds_find(int* parent, int x) {
+  while (true) {
+    const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (p == x) return x;
+    x = p;
+  }
+}
+
+// NT threads, rows t, t + NT, .. (at most kBatchEPT) per thread.  LIT: the
+// literal dot order (wave 0 folds every sum in ascending j, fold_chunk) --
+// bitwise k_fold_init + k_cg_small<true, true>; else per thread in row
+// order, wave butterfly, waves in order.
+template <int NT, bool LIT>
+__global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const Geom g = a.g;
+  const int m = g.m, T = g.t, N = a.N;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int item = blockIdx.x;
+  // labeling view of the arena
+  int* parent = reinterpret_cast<int*>(smem);
+  uint8_t* bocc = reinterpret_cast<uint8_t*>(smem + a.L.oBocc);
+  uint8_t* member = reinterpret_cast<uint8_t*>(smem + a.L.oMem);
+  uint8_t* flag = reinterpret_cast<uint8_t*>(smem + a.L.oFlag);
+  // solver view
+  double* s_p = reinterpret_cast<double*>(smem);
+  double* s_q = reinterpret_cast<double*>(smem + a.L.oQ);
+  uint16_t* s_c = reinterpret_cast<uint16_t*>(smem + a.L.oC);
+  double* s_red = reinterpret_cast<double*>(smem + a.L.oRed);
+  int* s_off = reinterpret_cast<int*>(smem + a.L.oOff);
+  StencilForms* sF = reinterpret_cast<StencilForms*>(smem + a.L.oF);
+  double* s_rhs = reinterpret_cast<double*>(smem + a.L.oRhs);
+  uint16_t* s_cur = reinterpret_cast<uint16_t*>(smem + a.L.oCur);
+  int* s_i = reinterpret_cast<int*>(smem + a.L.oInt);
+
+  const int count = a.item_count[item];
+  const int* __restrict__ rank = a.rank + (size_t)a.item_trial[item] * a.nb;
+  BatchOut* out = a.out + item;
+
+  // ---- occupancy: bond id is occupied iff its position in the order < count
+  {
+    const int nw = (int)(sizeof(StencilForms) / 4);
+    const int* src = reinterpret_cast<const int*>(a.forms);
+    int* dst = reinterpret_cast<int*>(sF);
+    for (int k = t; k < nw; k += NT) dst[k] = src[k];
+  }
+  if (t < 8) s_i[t] = t == 2 ? INT_MAX : 0;
+  for (int s = t; s <= T; s += NT) {
+    parent[s] = s;
+    member[s] = 0;
+  }
+  for (int c = t; c <= m; c += NT) flag[c] = 0;
+  for (int id = t; id < a.nb; id += NT) bocc[id] = rank[id] < count ? 1 : 0;
+  load_forms(*a.forms, s_off);  // (ends with a workgroup barrier)
+
+  // ---- labeling: hook the larger root under the smaller over every occupied
+  // bond, flatten, until a pass hooks nothing (the flag is workgroup-uniform)
+  for (int pass = 0;; ++pass) {
+    int changed = 0;
+    for (int s = t + 1; s < T; s += NT) {
+      const int sr = div_m(g, s - 1);
+      int nn[6];
+      nearestn_rc(g, s, sr, s - 1 - sr * m, nn);
+      int id = a.bond_first[s];
+      for (int k = 0; k < g.scn; ++k) {
+        const int q = nn[k];
+        if (q <= s) continue;
+        if (bocc[id]) {
+          if (pass == 0) {
+            member[s] = 1;
+            member[q] = 1;
+          }
+          const int ra = lds_find(parent, s), rb = lds_find(parent, q);
+          if (ra != rb) {
+            atomicMin(&parent[max(ra, rb)], min(ra, rb));
+            changed = 1;
+          }
+        }
+        ++id;
+      }
+    }
+    changed = __syncthreads_or(changed);
+    // each thread walks, then writes only its own entries
+    for (int s = t + 1; s <= T; s += NT) {
+      const int r = lds_find(parent, s);
+      __hip_atomic_store(&parent[s], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    if (!changed) break;
+  }
+
+  // ---- spanning (k_span_top's rule): root <= m and a top-row member
+  for (int c = t; c < m; c += NT) {
+    const int s = T - m + 1 + c;
+    if (member[s] && parent[s] <= m) flag[parent[s]] = 1;
+  }
+  __syncthreads();
+  {
+    int ncl = 0, nsp = 0, mn = INT_MAX;
+    for (int s = t + 1; s <= T; s += NT) ncl += parent[s] == s && member[s];
+    for (int c = t + 1; c <= m; c += NT)
+      if (flag[c]) {
+        ++nsp;
+        mn = min(mn, c);
+      }
+    if (ncl) atomicAdd(&s_i[0], ncl);
+    if (nsp) {
+      atomicAdd(&s_i[1], nsp);
+      atomicMin(&s_i[2], mn);
+    }
+  }
+  __syncthreads();
+  const int nclusters = s_i[0], nspan = s_i[1];
+  const int root = nspan > 0 ? s_i[2] : 0;
+  if (root) {
+    int cnt = 0;
+    for (int s = t + 1; s <= T; s += NT) cnt += member[s] && parent[s] == root;
+    if (cnt) atomicAdd(&s_i[3], cnt);
+  }
+  __syncthreads();
+  const int span_sites = s_i[3];
+  const bool stop = nspan != 1 || !a.solve;  // (uniform: LDS values after a barrier)
+  if (t == 0) {
+    out->nclusters = nclusters;
+    out->nspan = nspan;
+    out->span_root = root;
+    out->span_sites = span_sites;
+    out->fallback = nspan > 1 ? 1 : 0;  // the lowest-label rule: host replay
+    out->pad = 0;
+    if (stop) {
+      out->status = nspan == 0 ? 1 : 0;
+      out->iter = 0;
+      out->err = 0.0;
+    }
+  }
+  if (stop) return;
+
+  // ---- assembly: row codes into LDS, the top system row's rhs (the only
+  // rows with a non-zero one), the electrode rows' slot values as 2-bit codes
+  const double g0 = a.g0, leak = a.leak, Va = a.Va;
+#pragma unroll 1
+  for (int i = t; i < N; i += NT) {
+    uint16_t c;
+    double b;
+    assemble_row_vals<false>(g, i, a.bond_first, bocc, nullptr, parent, nullptr, nullptr, nullptr, &b,
+                             &c, a.sflag, *sF, a.fast, a.fl, a.fr, a.bf_closed, PERC_RULE_BOND, g0,
+                             leak, Va, root, nullptr);
+    s_c[i] = c;
+    if (i >= N - m) s_rhs[i - (N - m)] = b;
+  }
+#pragma unroll 1
+  for (int idx = t; idx < 2 * m; idx += NT) {
+    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
+    const int ps = parent[s];
+    int nbr[6];
+    const int cnt = sorted_neighbours(g, s, nbr);
+    unsigned cc = 0;
+    for (int j = 0; j < cnt; ++j) {
+      const int c = nbr[j];
+      const int id = s < c ? bond_id(g, a.bond_first, s, c) : bond_id(g, a.bond_first, c, s);
+      unsigned kind = 0;  // no bond: 0.0 (k_currents)
+      if (id >= 0)
+        kind = bond_value(PERC_RULE_BOND, id, s, c, ps, bocc, nullptr, root, g0, leak, nullptr) == -g0
+                   ? 2u
+                   : 1u;
+      cc |= kind << (2 * j);
+    }
+    s_cur[idx] = (uint16_t)cc;
+  }
+  __syncthreads();  // the labeling arrays are dead from here: p and q take their place
+
+  // ---- solve: k_cg_small<true, LIT>, the prologue included (x = 0, r = b)
+  const double ng0 = -g0, nleak = -leak;
+  double rv[kBatchEPT], dv[kBatchEPT], xv[kBatchEPT];
+#pragma unroll
+  for (int j = 0; j < kBatchEPT; ++j) {
+    const int i = t + j * NT;
+    const unsigned c = i < N ? (unsigned)s_c[i] : 0u;
+    rv[j] = i < N && i >= N - m ? s_rhs[i - (N - m)] : 0.0;
+    xv[j] = 0.0;
+    dv[j] = i < N ? code_diag(c, ng0, nleak) : 1.0;
+  }
+  // workgroup sum: per-wave butterfly, then the waves in order
+  auto wg_sum = [&](double v0, double v1, double* o0, double* o1) {
+    v0 = wave_sum(v0);
+    v1 = wave_sum(v1);
+    if (lane == 0) {
+      s_red[wid] = v0;
+      s_red[16 + wid] = v1;
+    }
+    __syncthreads();
+    double t0 = s_red[0], t1 = s_red[16];
+    for (int w = 1; w < NT / 64; ++w) {
+      t0 = t0 + s_red[w];
+      t1 = t1 + s_red[16 + w];
+    }
+    __syncthreads();  // s_red reuse
+    *o0 = t0;
+    *o1 = t1;
+  };
+  const int itol = a.itol, itmax = a.itmax;
+  const double tol = a.tol;
+  double bnrm, bknum;
+  if constexpr (LIT) {  // k_fold_init: bnrm^2 and the first bknum in ascending j
+#pragma unroll
+    for (int j = 0; j < kBatchEPT; ++j) {
+      const int i = t + j * NT;
+      if (i < N) s_q[i] = rv[j];
+    }
+    __syncthreads();
+    if (wid == 0) {
+      double acc[2] = {0.0, 0.0};
+      for (int j0 = 0; j0 < N; j0 += 64) {
+        const int j = min(j0 + lane, N - 1);
+        const double rj = s_q[j];
+        const double dj = code_diag(s_c[j], ng0, nleak);
+        const double zb = itol == 1 ? rj : rj / dj, z = rj / dj;
+        const double tz[2] = {zb * zb, z * rj};
+        fold_chunk<2>(tz, min(64, N - j0), acc);
+      }
+      if (lane == 0) {
+        s_red[32] = sqrt(acc[0]);
+        s_red[33] = acc[1];
+      }
+    }
+    __syncthreads();
+    bnrm = s_red[32];
+    bknum = s_red[33];
+    __syncthreads();
+  } else {
+    double b2 = 0.0, zr0 = 0.0;
+#pragma unroll
+    for (int j = 0; j < kBatchEPT; ++j) {
+      const int i = t + j * NT;
+      if (i < N) {
+        const double zb = itol == 1 ? rv[j] : rv[j] / dv[j], z = rv[j] / dv[j];
+        b2 = b2 + zb * zb;
+        zr0 = zr0 + z * rv[j];
+      }
+    }
+    double tb, tz;
+    wg_sum(b2, zr0, &tb, &tz);
+    bnrm = sqrt(tb);
+    bknum = tz;
+  }
+  double bk = 0.0, ak = 0.0, err = 0.0;
+  int k = 0;
+  while (true) {
+    ++k;
+    // p(k) = bk p(k-1) + z (k = 1: p = z), linbcg :789-797
+#pragma unroll
+    for (int j = 0; j < kBatchEPT; ++j) {
+      const int i = t + j * NT;
+      if (i < N) {
+        const double z = rv[j] / dv[j];
+        s_p[i] = k == 1 ? z : bk * s_p[i] + z;
+      }
+    }
+    __syncthreads();
+    // q = A p (dsprsax order) into LDS, and q.p
+    double dot = 0.0;
+#pragma unroll 1
+    for (int i = t; i < N; i += NT) {
+      const double pi = s_p[i];
+      const unsigned c = s_c[i];
+      const int f = c >> 11, cnt = (c >> 8) & 7;
+      double xn[kMaxSlots];
+      bool use[kMaxSlots];
+#pragma unroll
+      for (int e = 0; e < kMaxSlots; ++e) {
+        const int col = i + s_off[f * kMaxSlots + e];
+        use[e] = e < cnt && (unsigned)col < (unsigned)N;
+        xn[e] = s_p[use[e] ? col : i];
+      }
+      const double q = st_combine<kMaxSlots>(c, xn, use, pi, ng0, nleak);
+      dot = dot + q * pi;
+      s_q[i] = q;
+    }
+    double akden, unused;
+    if constexpr (LIT) {
+      __syncthreads();  // s_q complete
+      if (wid == 0) {
+        double acc[1] = {0.0};
+        for (int j0 = 0; j0 < N; j0 += 64) {
+          const int j = min(j0 + lane, N - 1);
+          const double tq[1] = {s_q[j] * s_p[j]};  // akden, bondc.f:803-805
+          fold_chunk<1>(tq, min(64, N - j0), acc);
+        }
+        if (lane == 0) s_red[32] = acc[0];
+      }
+      __syncthreads();
+      akden = s_red[32];
+      __syncthreads();
+    } else {
+      wg_sum(dot, 0.0, &akden, &unused);
+    }
+    ak = bknum / akden;
+    // x += ak p, r -= ak q, z = r/d, z.r and r.r (linbcg :801-806, 808-813)
+    double zr = 0.0, rr = 0.0;
+#pragma unroll
+    for (int j = 0; j < kBatchEPT; ++j) {
+      const int i = t + j * NT;
+      if (i < N) {
+        xv[j] = xv[j] + ak * s_p[i];
+        const double rn = rv[j] - ak * s_q[i];
+        rv[j] = rn;
+        const double z = rn / dv[j];
+        zr = zr + z * rn;
+        rr = rr + rn * rn;
+      }
+    }
+    double tzr, trr;
+    if constexpr (LIT) {
+      // r(k+1) through LDS (q is dead until the next iteration's)
+#pragma unroll
+      for (int j = 0; j < kBatchEPT; ++j) {
+        const int i = t + j * NT;
+        if (i < N) s_q[i] = rv[j];
+      }
+      __syncthreads();
+      if (wid == 0) {
+        double acc[2] = {0.0, 0.0};
+        for (int j0 = 0; j0 < N; j0 += 64) {
+          const int j = min(j0 + lane, N - 1);
+          const double rj = s_q[j];
+          const double zj = rj / code_diag(s_c[j], ng0, nleak);
+          const double tz[2] = {zj * rj, rj * rj};  // bknum :785-787, snrm :872-875
+          fold_chunk<2>(tz, min(64, N - j0), acc);
+        }
+        if (lane == 0) {
+          s_red[32] = acc[0];
+          s_red[33] = acc[1];
+        }
+      }
+      __syncthreads();
+      tzr = s_red[32];
+      trr = s_red[33];
+      __syncthreads();
+    } else {
+      wg_sum(zr, rr, &tzr, &trr);
+    }
+    err = sqrt(trr) / bnrm;
+    bk = tzr / bknum;
+    bknum = tzr;
+    // err comes from one LDS value in every thread: a uniform break
+    if (!(err > tol) || k >= itmax + 1) break;
+  }
+
+  // ---- currents: k_currents' PERC_CUR_FORTRAN expression on the 2m electrode
+  // sites, x through LDS (q is dead)
+#pragma unroll
+  for (int j = 0; j < kBatchEPT; ++j) {
+    const int i = t + j * NT;
+    if (i < N) s_q[i] = xv[j];
+  }
+  __syncthreads();
+  const double* x = s_q;
+  double* iout = a.iout + (size_t)item * 2 * m;
+#pragma unroll 1
+  for (int idx = t; idx < 2 * m; idx += NT) {
+    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
+    int nbr[6];
+    const int cnt = sorted_neighbours(g, s, nbr);
+    const unsigned cc = s_cur[idx];
+    double gv[6];
+    double rowsum = 0.0;
+    for (int j = 0; j < cnt; ++j) {
+      const unsigned kind = (cc >> (2 * j)) & 3u;
+      gv[j] = kind == 0 ? 0.0 : (kind == 2 ? -g0 : -leak);
+      rowsum = rowsum + gv[j];
+    }
+    const double d = -rowsum;
+    auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : x[c - m - 1]); };
+    double acc = d * V(s);
+    for (int j = 0; j < cnt; ++j)
+      if (fabs(gv[j]) >= 1.0e-10) acc = acc + gv[j] * V(nbr[j]);
+    iout[idx] = acc;
+  }
+  if (t == 0) {
+    out->status = 0;
+    out->iter = k;
+    out->err = err;
+  }
+}
+
+struct BatchState {
+  int* d_rank = nullptr;
+  size_t rank_cap = 0;
+  int ntrials = 0;
+  int* d_items = nullptr;  // item_trial, then item_count
+  BatchOut* d_out = nullptr;
+  double* d_iout = nullptr;
+  size_t item_cap = 0, iout_cap = 0;
+  int* d_sflag = nullptr;
+  int lds_attr[3][2] = {};  // dynamic LDS granted per instantiation
+};
+
+template <int NT, bool LIT>
+hipError_t launch(BatchState* B, int slot, const BatchArgs& a, int nitems, hipStream_t st) {
+  if (B->lds_attr[slot][LIT] < a.L.total) {  // dynamic LDS beyond the default limit
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_bondc<NT, LIT>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
+    B->lds_attr[slot][LIT] = a.L.total;
+  }
+  k_batch_bondc<NT, LIT><<<nitems, NT, a.L.total, st>>>(a);
+  return dbg_sync(st, "k_batch_bondc");
+}
+
+}  // namespace
+
+static BatchState* batch_state(perc_ctx* h) {
+  if (!h->batch) h->batch = new BatchState();
+  return static_cast<BatchState*>(h->batch);
+}
+
+void dev_batch_free(perc_ctx* h) {
+  BatchState* B = static_cast<BatchState*>(h->batch);
+  if (!B) return;
+  (void)hipFree(B->d_rank);
+  (void)hipFree(B->d_items);
+  (void)hipFree(B->d_out);
+  (void)hipFree(B->d_iout);
+  (void)hipFree(B->d_sflag);
+  delete B;
+  h->batch = nullptr;
+}
+
+hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank) {
+  BatchState* B = batch_state(h);
+  const size_t n = (size_t)ntrials * (size_t)h->nb;
+  if (B->rank_cap < n) {
+    if (B->d_rank) HIP_TRY(hipFree(B->d_rank));
+    B->d_rank = nullptr;
+    B->rank_cap = 0;
+    HIP_TRY(dmalloc(&B->d_rank, n));
+    B->rank_cap = n;
+  }
+  B->ntrials = ntrials;
+  if (!B->d_sflag) {
+    HIP_TRY(dmalloc(&B->d_sflag, 4));
+    HIP_TRY(hipMemsetAsync(B->d_sflag, 0, 4 * sizeof(int), h->stream));
+  }
+  if (n) HIP_TRY(hipMemcpyAsync(B->d_rank, rank, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  return hipStreamSynchronize(h->stream);  // (the caller's array may go away)
+}
+
+hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const int* item_count,
+                         int solve, double Va, double g0, double leak, int itol, double tol,
+                         int itmax, bool literal, BatchOut* out, double* iout) {
+  if (nitems == 0) return hipSuccess;
+  BatchState* B = batch_state(h);
+  hipStream_t st = h->stream;
+  const int m = h->g.m;
+  if (B->item_cap < (size_t)nitems) {
+    if (B->d_items) HIP_TRY(hipFree(B->d_items));
+    if (B->d_out) HIP_TRY(hipFree(B->d_out));
+    B->d_items = nullptr;
+    B->d_out = nullptr;
+    B->item_cap = 0;
+    HIP_TRY(dmalloc(&B->d_items, 2 * (size_t)nitems));
+    HIP_TRY(dmalloc(&B->d_out, (size_t)nitems));
+    B->item_cap = nitems;
+  }
+  const size_t niout = solve ? (size_t)nitems * 2 * m : 0;
+  if (B->iout_cap < niout) {
+    if (B->d_iout) HIP_TRY(hipFree(B->d_iout));
+    B->d_iout = nullptr;
+    B->iout_cap = 0;
+    HIP_TRY(dmalloc(&B->d_iout, niout));
+    B->iout_cap = niout;
+  }
+  HIP_TRY(hipMemcpyAsync(B->d_items, item_trial, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(B->d_items + nitems, item_count, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
+  // an item that stops before the currents leaves its iout row unwritten
+  if (niout) HIP_TRY(hipMemsetAsync(B->d_iout, 0, sizeof(double) * niout, st));
+  BatchArgs a;
+  a.g = h->g;
+  a.N = h->N;
+  a.nb = (int)h->nb;
+  a.bond_first = h->d.bond_first;
+  a.forms = h->d.forms_dev;
+  a.rank = B->d_rank;
+  a.item_trial = B->d_items;
+  a.item_count = B->d_items + nitems;
+  a.out = B->d_out;
+  a.iout = B->d_iout;
+  a.sflag = B->d_sflag;
+  asm_closed_forms(h, &a.fast, &a.fl, &a.fr);
+  a.bf_closed = h->bf_closed ? 1 : 0;
+  a.solve = solve;
+  a.itol = itol;
+  a.itmax = itmax;
+  a.Va = Va;
+  a.g0 = g0;
+  a.leak = leak;
+  a.tol = tol;
+  a.L = batch_lds(h->g);
+  const int nt = batch_threads(h->N);
+  hipError_t e;
+  if (nt == 256) e = literal ? launch<256, true>(B, 0, a, nitems, st) : launch<256, false>(B, 0, a, nitems, st);
+  else if (nt == 512) e = literal ? launch<512, true>(B, 1, a, nitems, st) : launch<512, false>(B, 1, a, nitems, st);
+  else e = literal ? launch<1024, true>(B, 2, a, nitems, st) : launch<1024, false>(B, 2, a, nitems, st);
+  HIP_TRY(e);
+  int flag = 0;
+  HIP_TRY(hipMemcpyAsync(out, B->d_out, sizeof(BatchOut) * nitems, hipMemcpyDeviceToHost, st));
+  if (niout) HIP_TRY(hipMemcpyAsync(iout, B->d_iout, sizeof(double) * niout, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&flag, B->d_sflag, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (flag & 3) {  // a row without its stencil bond or form: perc_batch_supported excludes it
+    set_error("k_batch_bondc: a row does not fit the stencil operator");
+    return hipErrorInvalidValue;
+  }
+  return hipSuccess;
+}
+
+}  // namespace perc

@@ -1,0 +1,218 @@
+// perc_batch_host.cpp -- host side of the batch path (include/perc.h:
+// perc_batch_supported, perc_batch_bondc): argument checks, the orders'
+// inverse permutations, the launch geometry, the fold of the terminal
+// currents and the single-path replay of the items several clusters span.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "perc_batch.h"
+
+namespace perc {
+
+BatchLds batch_lds(const Geom& g) {
+  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
+  const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
+  BatchLds L{};
+  L.oQ = up16(8 * N);
+  const int solver_end = L.oQ + up16(8 * N);
+  L.oBocc = up16(4 * ((long long)g.t + 1));
+  L.oMem = L.oBocc + up16(nb + 1);
+  L.oFlag = L.oMem + up16(g.t + 1);
+  const int label_end = L.oFlag + up16(g.m + 1);
+  L.oC = std::max(solver_end, label_end);
+  L.oRed = L.oC + up16(2 * N);
+  L.oOff = L.oRed + up16(48 * sizeof(double));
+  L.oF = L.oOff + up16(kMaxForms * kMaxSlots * sizeof(int));
+  L.oRhs = L.oF + up16(sizeof(StencilForms));
+  L.oCur = L.oRhs + up16(8LL * g.m);
+  L.oInt = L.oCur + up16(4LL * g.m);
+  L.total = L.oInt + 64;
+  return L;
+}
+
+int batch_threads(int N) {
+  int nt = N <= 256 * kBatchEPT ? 256 : (N <= 512 * kBatchEPT ? 512 : 1024);
+  if (const char* e = std::getenv("PERC_BATCH_THREADS")) {
+    const int v = std::atoi(e);
+    if ((v == 256 || v == 512 || v == 1024) && (long long)v * kBatchEPT >= N) nt = v;
+  }
+  return nt;
+}
+
+bool batch_supported(const Geom& g) {
+  if (g.n < 3 || g.m < 3) return false;
+  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  const long long N = (long long)(g.n - 2) * g.m;
+  if (N > kBatchRows) return false;
+  const StencilForms F = stencil_forms(g);
+  if (F.nforms <= 0) return false;
+  // every stencil bond present, every interior row one of the forms
+  // (k_assemble's sflag bits 1 and 2)
+  for (int s = g.m + 1; s <= g.t - g.m; ++s) {
+    int nb[6];
+    const int cnt = sorted_neighbours(g, s, nb);
+    bool form = false;
+    for (int f = 0; f < F.nforms && !form; ++f) {
+      bool same = F.cnt[f] == cnt;
+      for (int j = 0; j < cnt && same; ++j) same = F.off[f][j] == nb[j] - s;
+      form = same;
+    }
+    if (!form) return false;
+    for (int j = 0; j < cnt; ++j) {
+      const int lo = std::min(s, nb[j]), hi = std::max(s, nb[j]);
+      int nn[6];
+      nearestn(g, lo, nn);
+      bool bond = false;
+      for (int k = 0; k < g.scn; ++k) bond |= nn[k] == hi;
+      if (!bond) return false;
+    }
+  }
+  const BatchLds L = batch_lds(g);
+  return L.total + kBatchLdsStatic <= kBatchLdsMax;
+}
+
+int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders) {
+  const int nb = (int)h->nb;
+  hipSetDevice(h->device);
+  // rank[id - 1] = position of bond id in the order (the spill slot 0 takes a
+  // position and is no bond)
+  std::vector<int> rank((size_t)ntrials * nb, INT_MAX);
+  for (int tr = 0; tr < ntrials; ++tr) {
+    const int* o = orders + (size_t)tr * (nb + 1);
+    int* r = rank.data() + (size_t)tr * nb;
+    for (int pos = 0; pos <= nb; ++pos) {
+      const int id = o[pos];
+      if (id >= 1 && id <= nb && r[id - 1] == INT_MAX) r[id - 1] = pos;
+    }
+  }
+  hipError_t e = dev_batch_upload(h, ntrials, rank.data());
+  if (e != hipSuccess) return hip_status(e, "perc_batch_bondc/upload");
+  return PERC_OK;
+}
+
+int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
+                    const int* item_count, int solve, bool replay, double Va, double g0, double leak,
+                    int itol, double tol, int itmax, perc_batch_item* out) {
+  const int nb = (int)h->nb, m = h->g.m;
+  hipSetDevice(h->device);
+  hipError_t e;
+  const bool literal = h->dot_order != PERC_DOT_FAST;
+  // launches of bounded size (the iout rows: 16 m bytes per item)
+  const int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
+  std::vector<BatchOut> bo((size_t)std::min(nitems, chunk));
+  std::vector<double> iout(solve ? bo.size() * 2 * (size_t)m : 0);
+  std::vector<int> list;
+  for (int i0 = 0; i0 < nitems; i0 += chunk) {
+    const int n = std::min(chunk, nitems - i0);
+    e = dev_batch_run(h, n, item_trial + i0, item_count + i0, solve ? 1 : 0, Va, g0, leak, itol, tol,
+                      itmax, literal, bo.data(), iout.data());
+    if (e != hipSuccess) return hip_status(e, "perc_batch_bondc");
+    for (int i = 0; i < n; ++i) {
+      perc_batch_item& it = out[i0 + i];
+      const BatchOut& b = bo[i];
+      std::memset(&it, 0, sizeof(it));
+      it.nclusters = b.nclusters;
+      it.nspan = b.nspan;
+      it.span_root = b.span_root;
+      it.span_sites = b.span_sites;
+      it.fallback = b.fallback;
+      it.status = b.status;
+      it.iter = b.iter;
+      it.err = b.err;
+      if (b.fallback && replay) {
+        // several clusters span: the reference's lowest-label rule through
+        // the single path, on the context
+        const int* o = orders + (size_t)item_trial[i0 + i] * (nb + 1);
+        const int cnt = item_count[i0 + i];
+        const int* src = o;
+        int len = cnt;
+        if (cnt > nb) {  // the whole order: the spill slot dropped
+          list.clear();
+          for (int k = 0; k < cnt; ++k)
+            if (o[k] != 0) list.push_back(o[k]);
+          if ((int)list.size() > nb) return PERC_EINVAL;
+          src = list.data();
+          len = (int)list.size();
+        }
+        perc_label_info li{};
+        int rc = perc_occupy(h, PERC_BOND, 0, nullptr, len, src);
+        if (!rc) rc = perc_label(h, &li, nullptr);
+        if (rc) return rc;
+        it.nclusters = li.nclusters;
+        it.nspan = li.nspan;
+        it.span_root = li.span_root;
+        it.span_sites = li.span_sites;
+        if (solve) {
+          perc_cond_result res{};
+          rc = perc_conductance(h, PERC_RULE_BOND, PERC_CUR_FORTRAN, Va, g0, leak, itol, tol, itmax,
+                                &res, nullptr);
+          if (rc) return rc;
+          it.gtop = res.gtop;
+          it.gbot = res.gbot;
+          it.err = res.err;
+          it.iter = res.iter;
+          it.status = res.status;
+        }
+      } else if (solve && b.status == 0) {
+        // currents_impl's ascending fold (bondc.f:587-590)
+        const double* io = iout.data() + (size_t)i * 2 * m;
+        double Ibot = 0.0, Itop = 0.0;
+        for (int c = 0; c < m; ++c) {
+          Ibot = Ibot + io[c];
+          Itop = Itop + io[m + c];
+        }
+        it.gtop = Itop / Va;
+        it.gbot = std::fabs(Ibot) / Va;
+      }
+    }
+  }
+  return PERC_OK;
+}
+
+}  // namespace perc
+
+using namespace perc;
+
+extern "C" {
+
+int perc_batch_supported(int lattice, int m, int n, int pbc) {
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n >= (1LL << 31) - 16) return 0;
+  return batch_supported(make_geom(lattice, m, n, pbc)) ? 1 : 0;
+}
+
+int perc_batch_bondc(perc_ctx* h, int ntrials, const int* orders, int nitems, const int* item_trial,
+                     const int* item_count, int solve, double Va, double g0, double leak, int itol,
+                     double tol, int itmax, perc_batch_item* out) {
+  if (!h || ntrials < 0 || nitems < 0 || (ntrials && !orders) ||
+      (nitems && (!item_trial || !item_count || !out)) || itmax < 0)
+    return PERC_EINVAL;
+  if (solve && itol != 1 && itol != 2) {
+    set_error("perc_batch_bondc: itol 1 or 2 only");
+    return PERC_EINVAL;
+  }
+  if (!batch_supported(h->g)) {
+    set_error("perc_batch_bondc: lattice not supported by the batch kernel (perc_batch_supported)");
+    return PERC_EINVAL;
+  }
+  const int nb = (int)h->nb;
+  for (int i = 0; i < nitems; ++i)
+    if (item_trial[i] < 0 || item_trial[i] >= ntrials || item_count[i] < 0 || item_count[i] > nb + 1) {
+      set_error("perc_batch_bondc: item_trial outside 0..ntrials-1 or item_count outside 0..nb+1");
+      return PERC_EINVAL;
+    }
+  if (nitems == 0) return PERC_OK;
+  int rc = batch_upload_orders(h, ntrials, orders);
+  if (rc) return rc;
+  return batch_run_items(h, orders, nitems, item_trial, item_count, solve, true, Va, g0, leak, itol,
+                         tol, itmax, out);
+}
+
+}  // extern "C"

@@ -93,6 +93,56 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* s_red /*8*NV*
   }
 }
 
+// The literal dot order's serial fold (perc_cg.h, perc_batch.hip):
+// fold lanes 0 .. cnt-1 of t[c] into acc[c] in lane order (wave-uniform cnt;
+// one wave).  The terms go through a wave-private LDS row and every lane
+// reads them back as broadcasts, so the serial chain is one fp64 add per
+// term with an LDS operand (the v_readlane pair per term of the round-4
+// first version doubled the VALU work; config 2's literal solve then ran
+// 30.9 ms per iteration).  A wave's LDS instructions execute in order, so
+// a compiler barrier orders the stores before the reads and the reads
+// before the next chunk's stores.
+__device__ __forceinline__ void fold_lds_order() {
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
+}
+// A full chunk is read back in batches of U terms per sum -- U / 2 16-B
+// broadcast reads each, all issued before the batch's adds -- so the serial
+// chain waits for LDS once per batch instead of every few terms: 7.7 vs 13.7
+// ns per term of two sums (tools/fold_bench.hip, profiles/r5_2_fold_bench.json;
+// 16 in the fold kernels, 8 in the resident solve's register-bound literal
+// instantiation)
+template <int NC, int U = 16>
+__device__ __forceinline__ void fold_chunk(const double (&t)[NC], int cnt, double (&acc)[NC]) {
+  __shared__ __attribute__((aligned(16))) double s_t[NC][64];
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) s_t[c][lane] = t[c];
+  fold_lds_order();
+  if (cnt == 64) {
+#pragma unroll
+    for (int b = 0; b < 32; b += U / 2) {
+      double2 x[NC][U / 2];
+#pragma unroll
+      for (int i = 0; i < U / 2; ++i)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) x[c][i] = reinterpret_cast<const double2*>(s_t[c])[b + i];
+#pragma unroll
+      for (int i = 0; i < U / 2; ++i)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          acc[c] = acc[c] + x[c][i].x;  // terms 2(b+i), 2(b+i)+1 in order
+          acc[c] = acc[c] + x[c][i].y;
+        }
+    }
+  } else {
+    for (int l = 0; l < cnt; ++l)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[c] = acc[c] + s_t[c][l];
+  }
+  fold_lds_order();
+}
+
 // Nontemporal stores for the CG vectors each kernel writes and the next one
 // reads (p, q, r): they stream past L2 / the Infinity Cache instead of
 // evicting what the next kernel reads.  Measured on the real PS/B sequence

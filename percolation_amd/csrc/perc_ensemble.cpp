@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "perc_batch.h"
 #include "perc_internal.h"
 
 using namespace perc;
@@ -27,6 +28,7 @@ using namespace perc;
 struct perc_ensemble {
   int ndev = 0;
   int workers = 1;  // contexts (host threads, streams) per device
+  int batch = 0;    // perc_ensemble_set_batch: items per launch of the batch path (0: off)
   int lattice = 0, m = 0, n = 0, pbc = 0;
   std::vector<int> devices;
   std::vector<perc_ctx*> ctx;  // [d * workers + w]
@@ -188,6 +190,21 @@ int perc_ensemble_set_workers(perc_ensemble* e, int workers) {
 
 int perc_ensemble_workers(perc_ensemble* e) { return e ? e->workers : PERC_EINVAL; }
 
+// Batch path of perc_ensemble_bond_cond: about `items` (trial, grid point)
+// realisations per launch of k_batch_bondc, one workgroup each (0, the
+// default: the per-trial loop).  Ignored on a lattice perc_batch_supported
+// refuses: perc_ensemble_batch then returns 0.
+int perc_ensemble_set_batch(perc_ensemble* e, int items) {
+  if (!e || items < 0) return PERC_EINVAL;
+  e->batch = items;
+  return PERC_OK;
+}
+
+int perc_ensemble_batch(perc_ensemble* e) {
+  if (!e) return PERC_EINVAL;
+  return e->batch > 0 && perc_batch_supported(e->lattice, e->m, e->n, e->pbc) ? e->batch : 0;
+}
+
 // stats[d*k .. d*k+k) is device d's vector; on return every slice holds the
 // element-wise sum over the devices (ncclAllReduce, sum, fp64).
 int perc_ensemble_allreduce(perc_ensemble* e, double* stats, int k) {
@@ -224,6 +241,138 @@ int perc_ensemble_allreduce(perc_ensemble* e, double* stats, int k) {
   return PERC_OK;
 }
 
+// perc_ensemble_bond_cond with the batch path on: per device one host thread
+// takes its trials in groups of about `items` grid-point realisations.  A
+// group's orders are shuffled on the host and uploaded once (as rank arrays);
+// one launch solves every (trial, grid point) of the group, then the first
+// spanning count of every trial is bisected with one label-only launch over
+// the group per step, and perccln comes from the host replay.  Same stop
+// rules, outputs and statistics (accumulated in ascending trial order) as
+// the per-trial loop.
+static int bond_cond_batched(perc_ensemble* e, int ntrials, const int* tseed, int npts,
+                             const int* nbarr, double Va, double g0, double tol, int itmax,
+                             int* nrows, double* gbot, double* gtop, int* iters, int* bf_c,
+                             int* perccln, double* stats) {
+  const int ndev = e->ndev, W = e->workers, items = e->batch;
+  const int nb = perc_nbonds(e->lattice, e->m, e->n, e->pbc);
+  // the sweep's rows (bond_cond.f:392-483): the same for every trial
+  int R = 0;
+  for (int lastbf = -1; R < npts; ++R) {
+    const int bf = nbarr[R];
+    if (bf <= 0 || bf <= lastbf || bf > nb) break;  // a repeated nbarr stalls (H3)
+    lastbf = bf;
+  }
+  const int G = std::max(1, items / std::max(1, R));  // trials per launch
+  std::vector<double> acc((size_t)ndev * npts * 5, 0.0);
+  std::vector<int> rcs(ndev, PERC_OK);
+  std::vector<std::string> errs(ndev);
+  auto worker = [&](int d) {
+    perc_ctx* h = e->ctx[(size_t)d * W];
+    hipSetDevice(e->devices[d]);
+    double* a = acc.data() + (size_t)d * npts * 5;
+    std::vector<int> trials, orders, it_tr, it_cnt, lo, hi;
+    std::vector<perc_batch_item> out;
+    auto fail = [&](int rc) {
+      rcs[d] = rc;
+      errs[d] = perc_last_error();
+    };
+    for (int ii0 = d + 1; ii0 <= ntrials; ii0 += ndev * G) {
+      trials.clear();
+      for (int ii = ii0; ii <= ntrials && (int)trials.size() < G; ii += ndev) trials.push_back(ii - 1);
+      const int g = (int)trials.size();
+      orders.resize((size_t)g * (nb + 1));
+      for (int k = 0; k < g; ++k)  // bond_cond.f:181-193
+        perc_shuffle_seeded(tseed[trials[k]], nb, orders.data() + (size_t)k * (nb + 1));
+      int rc = batch_upload_orders(h, g, orders.data());
+      if (rc) return fail(rc);
+      // every grid point of every trial of the group: one launch
+      it_tr.clear();
+      it_cnt.clear();
+      for (int k = 0; k < g; ++k)
+        for (int jj = 0; jj < R; ++jj) {
+          it_tr.push_back(k);
+          it_cnt.push_back(nbarr[jj]);
+        }
+      out.resize(std::max<size_t>(it_tr.size(), (size_t)g));
+      rc = batch_run_items(h, orders.data(), (int)it_tr.size(), it_tr.data(), it_cnt.data(), 1, true,
+                           Va, g0, 1.0e-12, 2, tol, itmax, out.data());
+      if (rc) return fail(rc);
+      for (int k = 0; k < g; ++k) {
+        const int t = trials[k];
+        for (int jj = 0; jj < R; ++jj) {
+          const perc_batch_item& r = out[(size_t)k * R + jj];
+          const size_t o = (size_t)t * npts + jj;
+          gbot[o] = r.gbot;
+          gtop[o] = r.gtop;
+          iters[o] = r.iter;
+          double* s = a + (size_t)jj * 5;
+          s[0] += 1.0;
+          s[1] += r.gtop;
+          s[2] += r.gtop * r.gtop;
+          s[3] += r.nspan > 0 ? 1.0 : 0.0;
+          s[4] += r.iter;
+        }
+        nrows[t] = R;
+      }
+      // pc (bond_cond.f:353-389): spanning with every bond, then the
+      // bisection of perc_first_spanning, a label-only launch per step
+      it_tr.resize(g);
+      it_cnt.assign(g, nb);
+      for (int k = 0; k < g; ++k) it_tr[k] = k;
+      rc = batch_run_items(h, orders.data(), g, it_tr.data(), it_cnt.data(), 0, false, Va, g0, 1.0e-12,
+                           2, tol, itmax, out.data());
+      if (rc) return fail(rc);
+      lo.assign(g, 0);
+      hi.assign(g, 0);
+      for (int k = 0; k < g; ++k) hi[k] = out[k].nspan > 0 ? nb : 0;
+      while (true) {
+        it_tr.clear();
+        it_cnt.clear();
+        for (int k = 0; k < g; ++k)
+          if (hi[k] - lo[k] > 1) {
+            it_tr.push_back(k);
+            it_cnt.push_back(lo[k] + (hi[k] - lo[k]) / 2);
+          }
+        if (it_tr.empty()) break;
+        rc = batch_run_items(h, orders.data(), (int)it_tr.size(), it_tr.data(), it_cnt.data(), 0, false,
+                             Va, g0, 1.0e-12, 2, tol, itmax, out.data());
+        if (rc) return fail(rc);
+        for (size_t i = 0; i < it_tr.size(); ++i) {
+          const int k = it_tr[i];
+          if (out[i].nspan > 0) hi[k] = it_cnt[i];
+          else lo[k] = it_cnt[i];
+        }
+      }
+      for (int k = 0; k < g; ++k) {
+        const int t = trials[k];
+        int pl = 0;
+        if (hi[k] > 0) {  // the final lowest spanning label (bond_cond.f:486-496): host replay
+          int st[4] = {0, 0, 0, 0};
+          rc = perc_replay_labels(e->lattice, e->m, e->n, e->pbc, PERC_BOND, 0, nullptr, nb,
+                                  orders.data() + (size_t)k * (nb + 1), nullptr, nullptr, nullptr, 0,
+                                  st);
+          if (rc) return fail(rc);
+          pl = st[3];
+        }
+        perccln[t] = pl;
+        bf_c[t] = hi[k];
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int d = 0; d < ndev; ++d) th.emplace_back(worker, d);
+  for (auto& x : th) x.join();
+  for (int d = 0; d < ndev; ++d)
+    if (rcs[d]) {
+      set_error("perc_ensemble_bond_cond (batch): " + errs[d]);
+      return rcs[d];
+    }
+  const int rc = perc_ensemble_allreduce(e, acc.data(), npts * 5);
+  if (rc) return rc;
+  if (stats) std::memcpy(stats, acc.data(), sizeof(double) * npts * 5);
+  return PERC_OK;
+}
+
 int perc_ensemble_bond_cond(perc_ensemble* e, int ntrials, const int* tseed, int npts,
                             const int* nbarr, double Va, double g0, double tol, int itmax,
                             int* nrows, double* gbot, double* gtop, int* iters, int* bf_c,
@@ -231,6 +380,9 @@ int perc_ensemble_bond_cond(perc_ensemble* e, int ntrials, const int* tseed, int
   if (!e || ntrials < 0 || !tseed || npts < 0 || (npts && !nbarr) || !nrows || !bf_c ||
       !perccln || (npts && (!gbot || !gtop || !iters)))
     return PERC_EINVAL;
+  if (perc_ensemble_batch(e) > 0)
+    return bond_cond_batched(e, ntrials, tseed, npts, nbarr, Va, g0, tol, itmax, nrows, gbot, gtop,
+                             iters, bf_c, perccln, stats);
   const int ndev = e->ndev, W = e->workers;
   const int nb = perc_nbonds(e->lattice, e->m, e->n, e->pbc);
   // per worker, then summed per device in worker order

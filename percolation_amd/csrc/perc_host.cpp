@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "perc_batch.h"
 #include "perc_internal.h"
 
 namespace perc {
@@ -273,6 +274,7 @@ int perc_ctx_destroy(perc_ctx* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->dslab) dev_dslab_end(h, false);
   dslab_comm_release(h);
+  dev_batch_free(h);
   free_buffers(h);
   for (int i = 0; i < 8; ++i)
     if (h->ev[i]) hipEventDestroy(h->ev[i]);

@@ -265,6 +265,7 @@ struct perc_ctx {
   hipEvent_t ev_next[2] = {nullptr, nullptr};  // klaunch: start/stop of the next CG launch
   perc::KernelTiming timing;
   perc::MarchKnobs knobs;  // as the current dev_solve / dev_bench read them
+  void* batch = nullptr;   // perc_batch_bondc's device buffers (perc_batch.hip), made on first use
 };
 
 namespace perc {

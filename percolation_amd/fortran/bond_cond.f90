@@ -15,7 +15,7 @@
 !
 ! Parameters: the reference's block (10x10, numtrials 1, master seed 58302),
 ! overridable by bond_cond.nml (&bond_cond_nml lattice, m, n, pbc,
-! numtrials, seed, Va, g0, tol, itmax, device, ndev, workers /).  Output: bondcond.txt as
+! numtrials, seed, Va, g0, tol, itmax, device, ndev, workers, batch /).  Output: bondcond.txt as
 ! the reference writes it (bond_cond.f:107-117, 481-496).
 !
 ! ndev >= 1 shards the trials over devices 0..ndev-1 of the node
@@ -26,16 +26,19 @@
 ! on `device` in this thread.  workers > 1 (with ndev >= 1) runs that many
 ! trials at a time on each device (perc_ensemble_set_workers: a context,
 ! host thread and stream each) -- small lattices leave a device mostly idle.
+! batch > 0 (with ndev >= 1) takes about that many (trial, grid point)
+! realisations per launch of the batch kernel, one workgroup each
+! (perc_ensemble_set_batch; ignored where perc_batch_supported says 0).
 program bond_cond
   use perc_api
   implicit none
 #ifndef PERC_LATTICE
 #define PERC_LATTICE 0
 #endif
-  integer(c_int) :: lattice, m, n, pbc, numtrials, seed, itmax, device, ndev, workers
+  integer(c_int) :: lattice, m, n, pbc, numtrials, seed, itmax, device, ndev, workers, batch
   double precision :: Va, g0, tol
   namelist /bond_cond_nml/ lattice, m, n, pbc, numtrials, seed, Va, g0, tol, itmax, device, &
-                           ndev, workers
+                           ndev, workers, batch
   integer(c_int) :: t, nb, i, ii, jj, bf, lastbf, npts, lo, hi, mid, bfc, perccln, stats(4)
   integer(c_int) :: tseed(1000), nbarr(250)
   double precision :: pbarr(250), pb, pc, Gtop, Gbot
@@ -61,6 +64,7 @@ program bond_cond
   device = 0
   ndev = 0
   workers = 1
+  batch = 0
   if (perc_have_file('bond_cond.nml')) then
     open(newunit=u, file='bond_cond.nml', status='old')
     read(u, nml=bond_cond_nml)
@@ -107,6 +111,7 @@ program bond_cond
                     'perc_ensemble_create')
     if (workers > 1) call perc_check(perc_ensemble_set_workers(ens, workers), &
                                      'perc_ensemble_set_workers')
+    if (batch > 0) call perc_check(perc_ensemble_set_batch(ens, batch), 'perc_ensemble_set_batch')
     call perc_check(perc_ensemble_bond_cond(ens, numtrials, tseed, 250, nbarr, Va, g0, tol, &
                     itmax, e_nrows, e_gbot, e_gtop, e_iters, e_bfc, e_pl, e_stats), &
                     'perc_ensemble_bond_cond')

@@ -272,6 +272,27 @@ module perc_api
       integer(c_int), value :: workers
     end function perc_ensemble_set_workers
 
+    ! batch path of perc_ensemble_bond_cond: about `items` (trial, grid point)
+    ! realisations per launch, one workgroup each (0: the per-trial loop)
+    integer(c_int) function perc_ensemble_set_batch(e, items) &
+        bind(C, name='perc_ensemble_set_batch')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: e
+      integer(c_int), value :: items
+    end function perc_ensemble_set_batch
+
+    integer(c_int) function perc_ensemble_batch(e) bind(C, name='perc_ensemble_batch')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: e
+    end function perc_ensemble_batch
+
+    ! host-only: 1 when the batch kernel can run this lattice
+    integer(c_int) function perc_batch_supported(lattice, m, n, pbc) &
+        bind(C, name='perc_batch_supported')
+      import :: c_int
+      integer(c_int), value :: lattice, m, n, pbc
+    end function perc_batch_supported
+
     integer(c_int) function perc_ensemble_bond_cond(e, ntrials, tseed, npts, nbarr, Va, g0, &
         tol, itmax, nrows, gbot, gtop, iters, bf_c, perccln, stats) &
         bind(C, name='perc_ensemble_bond_cond')

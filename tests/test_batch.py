@@ -9,6 +9,8 @@ path (perc_occupy / perc_label / perc_conductance) item by item:
 * the fast order: deterministic, independent of the item's place in the
   grid, as accurate as the project asks of a re-associated solve
   (test_config_goldens.py: 2 trunc + max(1e-10, tol));
+* non-unit Va, g0 and leak, the leak on both sides of the 1e-10 threshold of
+  the currents: the literal order bitwise the single path and the oracle;
 * the size cap (N = 8192), a ragged last thread row (N = 8190), the H2 spill
   slot, a forced two-cluster fallback, the ensemble switch and the Fortran
   driver's `batch` key.
@@ -21,6 +23,8 @@ import numpy as np
 import pytest
 
 import golden_io as G
+import oracle_lib as O
+import rule_systems as R
 from percolation_amd import _lib as L
 from percolation_amd import api
 
@@ -214,6 +218,55 @@ def test_fast_order_accuracy():
                   % (ref["trial"][i], ref["count"][i], d, o["iter"], c["iter"]))
         worst = max(worst, d)
     print("worst relative distance to the literal result: %.3e" % worst)
+
+
+@pytest.mark.parametrize("Va,g0,leak", R.NONUNIT, ids=["leak_dropped", "leak_kept"])
+@pytest.mark.parametrize("lat", [(0, 10, 10, 0), (0, 50, 50, 0), (1, 12, 10, 1)])
+def test_nonunit_values_literal_bitwise(lat, Va, g0, leak):
+    """Va, g0 and leak that are no powers of two (no product exact), the
+    leak below and above the 1e-10 threshold of the Fortran-rule currents
+    (3e-9: the kernel's `>= 1e-10` keep branch runs): three trials at pb ~
+    0.45, 0.6, 0.8 and 1.0 in the literal order, bitwise the single path with
+    the same values and, on the 50 x 50 lattice, the oracle's linbcg and
+    currents (or_bond_values / or_assemble / or_currents with g0, leak, Va)."""
+    lattice, m, n, pbc = lat
+    assert api.batch_supported(*lat)
+    seeds = api.trial_seeds(58302, 3)
+    b1, b2 = api.bond_list(*lat)
+    nb = len(b1)
+    orders = np.stack([api.shuffled_ids(nb, int(s)) for s in seeds])
+    items = [(tr, int(pb * nb)) for tr in range(3) for pb in (0.45, 0.6, 0.8, 1.0)]
+    it = np.array([x[0] for x in items], np.int32)
+    ic = np.array([x[1] for x in items], np.int32)
+    with api.Context(*lat) as ctx:
+        ctx.set_dot_order(L.DOT_LITERAL)
+        out = ctx.batch_bondc(orders, it, ic, Va=Va, g0=g0, leak=leak, tol=TOL, itmax=ITMAX)
+        multi = spanning = 0
+        for o, (tr, cnt) in zip(out, items):
+            ctx.occupy(L.BOND, bond_order=orders[tr], nbonds_=cnt)
+            li = ctx.label()
+            c = ctx.conductance(L.RULE_BOND, L.CUR_FORTRAN, Va, g0, leak, 2, TOL, ITMAX)
+            for k in LABEL_KEYS:
+                assert o[k] == li[k], (k, tr, cnt, o, li)
+            for k in COND_KEYS:
+                assert o[k] == c[k], (k, tr, cnt, o, c)
+            multi += li["nspan"] > 1
+            if li["nspan"] == 0:
+                assert o["status"] == 1 and o["gtop"] == 0.0 and o["gbot"] == 0.0
+                continue
+            spanning += 1
+            assert o["status"] == 0 and o["gtop"] > 0.0 and o["iter"] <= ITMAX
+            if (m, n) != (50, 50):
+                continue
+            ref = api.replay_labels(lattice, m, n, pbc, L.BOND, bond_order=orders[tr], nbond=cnt)
+            gval = O.f64(nb)
+            O.lib().or_bond_values(0, nb, b1, b2, ref["bond_label"], O.i32(1), ref["perccln"], g0, leak, gval)
+            oc = O.conductance(lattice, m, n, pbc, b1, b2, gval, Va=Va, tol=TOL, itmax=ITMAX, cur_rule=0,
+                               cur_thresh=1e-10)
+            for k in ("gtop", "gbot", "iter", "err"):
+                assert o[k] == oc[k], (k, tr, cnt, o[k], oc[k])
+    print("lattice %s: %d / %d items span, %d with nspan > 1" % (lat, spanning, len(items), multi))
+    assert spanning >= 6 and multi <= 0.10 * len(items)
 
 
 @pytest.mark.parametrize("m,n", [(64, 130), (90, 93)])

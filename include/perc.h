@@ -622,6 +622,55 @@ int perc_batch_bondc(perc_ctx *h, int ntrials, const int *orders /* ntrials x (n
                      double Va, double g0, double leak, int itol, double tol, int itmax,
                      perc_batch_item *out);
 
+/* ---- batch of small threshold scans (one workgroup each) -------------- *
+ * The reference's threshold programs (Fortran/Square/bond_perc.f:204-366,
+ * site_perc.f:150-256, sb_perc.f:104-372, bs_perc.f:104-395) are ensembles
+ * of 10 .. 10^5 trials on lattices of 10 x 10 .. 50 x 50, each "fill one
+ * order until a cluster spans".  perc_batch_scan runs many trials in one
+ * launch: one workgroup takes trial i from its rank arrays (an element is
+ * occupied at count c iff its position in the order < c; the spill slot 0
+ * takes a position and is no element) through the whole bisection of
+ * perc_first_spanning / perc_first_spanning_mixed -- label at N, then
+ * lo = 0, hi = N, mid = lo + (hi - lo) / 2 until hi - lo == 1 -- with the
+ * union-find labeling and the spanning rule of perc_batch_bondc in LDS, no
+ * host round trip and no second launch, then labels once more at the first
+ * spanning count (at N when nothing spans) for the cluster sizes of
+ * perc_cluster_sizes.
+ *   kind PERC_BOND   bonds scanned; sizes in bonds (bond_perc.txt's columns)
+ *   kind PERC_SITE   sites scanned; a bond connects two occupied sites;
+ *                    sizes in sites (site_perc.txt's columns)
+ *   kind PERC_SITEBOND, scan PERC_BOND (sb_perc): the first fixed[i] entries
+ *                    of trial i's site order occupied, bonds scanned; a bond
+ *                    connects when it and both end sites are occupied
+ *   kind PERC_SITEBOND, scan PERC_SITE (bs_perc's intended rule, hazard H11):
+ *                    the first fixed[i] bonds occupied, sites scanned
+ * out[i].first = the first spanning count (0: nothing spans, as
+ * perc_first_spanning), maxcs / span_size = perc_cluster_sizes' numbers at
+ * that count (at N when nothing spans, span_size 0 then; both 0 for
+ * PERC_SITEBOND), nspan = the number of spanning clusters there (1 at a
+ * first spanning count: the element just added lies in one cluster).
+ * kind PERC_BOND / PERC_SITE: scan is ignored, fixed and the other kind's
+ * orders may be NULL.  site_orders: ntrials rows of t + 1 entries,
+ * bond_orders: ntrials rows of nb + 1, as perc_shuffle leaves them; the
+ * scanned prefix ranges over the first N entries (N = nb or t), as
+ * perc_first_spanning(order, N).  The call chunks itself so that one
+ * launch's rank arrays stay under 64 MB of device memory, and leaves the
+ * context's single-realisation state (occupancy, labeling, assembled system)
+ * untouched.  ntrials == 0 is PERC_OK.  PERC_EINVAL (text in
+ * perc_last_error): a lattice perc_scan_supported refuses, a bad kind or
+ * scan, a missing order list, fixed[i] outside 0..t (scan PERC_BOND) /
+ * 0..nb (scan PERC_SITE), ntrials < 0. */
+typedef struct { int first, maxcs, span_size, nspan; } perc_scan_item;
+/* host-only: 1 when the scan kernel can run this lattice: m, n >= 3 and
+   m*n <= 16384 sites (128 x 128; the workgroup's LDS arena).  The kernel's
+   own limits only: perc_ctx_create's rules (even m on the triangular
+   lattice, H7) stand beside it. */
+int perc_scan_supported(int lattice, int m, int n, int pbc);
+int perc_batch_scan(perc_ctx *h, int kind, int scan, int ntrials,
+                    const int *site_orders /* ntrials x (t+1) */,
+                    const int *bond_orders /* ntrials x (nb+1) */,
+                    const int *fixed, perc_scan_item *out);
+
 /* ---- ensemble statistics (bond_cond, config 4) ----------------------- */
 /* Accumulate stats for one pb point: {count, sum G, sum G^2, count spanning,
    sum iter} into acc[5*point..]. */
@@ -653,9 +702,9 @@ int perc_ensemble_workers(perc_ensemble *e);
    with items > 0 and a lattice perc_batch_supported accepts, each device's
    trials run in groups of about `items` (trial, grid point) realisations --
    the orders shuffled on the host (perc_shuffle_seeded), one
-   perc_batch_bondc launch per group for the conductances, bf_c by a
-   bisection whose every step is one label-only launch over the group's
-   trials, perccln by perc_replay_labels -- with the per-trial loop's stop
+   perc_batch_bondc launch per group for the conductances, bf_c by one
+   scan launch over the group's trials (one workgroup bisects each, as
+   perc_batch_scan), perccln by perc_replay_labels -- with the per-trial loop's stop
    rules, outputs and statistics (accumulated in ascending trial order; the
    workers setting is not used).  Gtop / Gbot differ from the per-trial
    loop's only by the association of the fast dot order's sums (bitwise the

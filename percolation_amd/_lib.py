@@ -55,6 +55,10 @@ class BatchItem(C.Structure):
                 ("span_root", C.c_int), ("span_sites", C.c_int), ("fallback", C.c_int)]
 
 
+class ScanItem(C.Structure):
+    _fields_ = [("first", C.c_int), ("maxcs", C.c_int), ("span_size", C.c_int), ("nspan", C.c_int)]
+
+
 class DslabBufs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("part_out", "part_all", "edge_lo", "edge_hi",
                                           "ghost_lo", "ghost_hi")]
@@ -180,6 +184,8 @@ SIGNATURES = {
     "perc_batch_supported": (C.c_int, [C.c_int] * 4),
     "perc_batch_bondc": (C.c_int, [_VP, C.c_int, _I, C.c_int, _I, _I, C.c_int, C.c_double,
                                    C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _VP]),
+    "perc_scan_supported": (C.c_int, [C.c_int] * 4),
+    "perc_batch_scan": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
     "perc_ensemble_ctx": (C.c_void_p, [_VP, C.c_int]),
     "perc_ensemble_trials": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP]),
     "perc_ensemble_allreduce": (C.c_int, [_VP, _D, C.c_int]),

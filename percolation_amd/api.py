@@ -99,6 +99,12 @@ def batch_supported(lattice, m, n, pbc=0):
     return bool(L.lib().perc_batch_supported(lattice, m, n, pbc))
 
 
+def scan_supported(lattice, m, n, pbc=0):
+    """perc_scan_supported (host-only): True when the scan kernel can run this
+    lattice -- m, n >= 3 and m * n <= 16384 sites."""
+    return bool(L.lib().perc_scan_supported(lattice, m, n, pbc))
+
+
 class Context:
     """One libperc context (one lattice on one device)."""
 
@@ -355,6 +361,37 @@ class Context:
                                          C.cast(out, C.c_void_p)), "perc_batch_bondc")
         return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
 
+    def batch_scan(self, kind, site_orders=None, bond_orders=None, scan=L.BOND, fixed=None):
+        """perc_batch_scan: many small threshold-scan trials in one launch,
+        one workgroup bisecting each.  kind BOND / SITE: the scanned list's
+        orders, (ntrials, N + 1) shuffled id arrays (one array for one
+        trial); kind SITEBOND: both lists, scan names the scanned one and
+        fixed (an int or one per trial) the occupied entries of the other.
+        Returns one dict per trial (first, maxcs, span_size, nspan)."""
+        so = bo = fx = None
+        ntrials = None
+        if site_orders is not None:
+            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
+            ntrials = so.shape[0]
+        if bond_orders is not None:
+            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
+            if ntrials is not None and bo.shape[0] != ntrials:
+                raise ValueError("site_orders and bond_orders differ in trials")
+            ntrials = bo.shape[0]
+        if fixed is not None:
+            fx = np.ascontiguousarray(fixed, dtype=np.int32).reshape(-1)
+            if ntrials is not None and len(fx) == 1:
+                fx = np.full(ntrials, fx[0], dtype=np.int32)
+            if ntrials is not None and len(fx) != ntrials:
+                raise ValueError("fixed: one value, or one per trial")
+            ntrials = len(fx)
+        if ntrials is None:
+            ntrials = 1  # (no list at all: libperc reports it)
+        out = (L.ScanItem * max(ntrials, 1))()
+        L.check(L.lib().perc_batch_scan(self.h, int(kind), int(scan), ntrials, L.ptr(so), L.ptr(bo),
+                                        L.ptr(fx), C.cast(out, C.c_void_p)), "perc_batch_scan")
+        return [{k: getattr(out[i], k) for k, _ in L.ScanItem._fields_} for i in range(ntrials)]
+
     def bondc_realisation(self, order, tbonds, Va=1.0, g0=1.0, tol=1e-8, itmax=2500,
                           device_ptr=None):
         """occupy + label + conductance.  `order` is a host int32 array, or
@@ -543,20 +580,35 @@ def first_spanning(ctx, order, kind=L.BOND, n=None):
 
 
 def threshold_scan(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, master=58302, numtrials=10,
-                   ctx=None, device=0, replay=False):
+                   ctx=None, device=0, replay=False, batch=0):
     """bond_perc / site_perc (Fortran/Square/bond_perc.f, site_perc.f): per
     trial ii, seed tseed(ii) = int(rand(0)*1e6)+1, the reference shuffle,
     then the first occupation count that spans; the record is (tseed,
     fraction = REAL*4 count/N, largest cluster size, spanning cluster size)
     at that step (the whole order if nothing spans), sizes on the GPU
     (perc_cluster_sizes; replay=True: by the host label replay, which also
-    gives the reference label number perccln)."""
+    gives the reference label number perccln).  batch > 0 (on a lattice
+    scan_supported accepts, without replay): the orders of `batch` trials at
+    a time shuffled on the host, one perc_batch_scan call per group -- the
+    same records."""
     own = ctx is None
     ctx = ctx or Context(lattice, m, n, pbc, device)
     try:
         N = ctx.nb if kind == L.BOND else ctx.t
         seeds = trial_seeds(master, max(numtrials, 1), scale=1000000)
         out = []
+        if batch > 0 and not replay and scan_supported(ctx.lattice, ctx.m, ctx.n, ctx.pbc):
+            for i0 in range(0, numtrials, batch):
+                sd = seeds[i0:min(i0 + batch, numtrials)]
+                orders = np.stack([shuffled_ids(N, int(s)) for s in sd])
+                res = ctx.batch_scan(kind, **{"bond_orders" if kind == L.BOND else "site_orders": orders})
+                for s, r in zip(sd, res):
+                    c = r["first"] if r["first"] else N
+                    out.append(dict(tseed=int(s), count=c,
+                                    f=float(np.float32(np.float32(c) / np.float32(N))),
+                                    maxcs=r["maxcs"], perccls=r["span_size"] if r["first"] else 0,
+                                    perccln=None))
+            return out
         for ii in range(numtrials):
             order = shuffled_ids(N, int(seeds[ii]))
             first = first_spanning(ctx, order, kind, N)
@@ -613,7 +665,7 @@ def paired_seeds(pseed, k=1000):
 
 
 def mixed_scan(lattice=0, m=50, n=50, pbc=0, scan=L.BOND, master=8811064, points=None,
-               iters=100, as_built=True, ctx=None, device=0):
+               iters=100, as_built=True, ctx=None, device=0, batch=0):
     """sb_perc (scan=BOND: sites fixed at ps, bonds added until a mixed
     cluster spans; Square/sb_perc.f) / bs_perc (scan=SITE: bonds fixed at
     pb, sites added; Square/bs_perc.f).  points: the ps (sb) / pb (bs)
@@ -622,7 +674,10 @@ def mixed_scan(lattice=0, m=50, n=50, pbc=0, scan=L.BOND, master=8811064, points
     pb); the scanned fraction is 0 when nothing spans.  sb_perc's first
     spanning bond count is the GPU bisection (perc_first_spanning_mixed);
     bs_perc's is the host replay of the reference as built (as_built, hazard
-    H11) or, with as_built=False, the GPU bisection of the intended rule."""
+    H11) or, with as_built=False, the GPU bisection of the intended rule.
+    batch > 0 (on a lattice scan_supported accepts; not the as-built bs_perc,
+    a host replay): the GPU bisections of `batch` trials at a time in one
+    perc_batch_scan call -- the same records."""
     own = ctx is None
     ctx = ctx or Context(lattice, m, n, pbc, device)
     try:
@@ -635,6 +690,26 @@ def mixed_scan(lattice=0, m=50, n=50, pbc=0, scan=L.BOND, master=8811064, points
                 points = [0.30 + 0.01 * i for i in range(71)]
         pseed = trial_seeds(master, 100)
         out = []
+        if (batch > 0 and not (scan == L.SITE and as_built)
+                and scan_supported(ctx.lattice, ctx.m, ctx.n, ctx.pbc)):
+            for ii, pt in enumerate(points):
+                ss, bs = paired_seeds(pseed[ii])
+                fx = int(pt * t) if scan == L.BOND else int(pt * nb)  # sb_perc.f:210, bs_perc.f:209
+                for j0 in range(0, iters, batch):
+                    jr = range(j0, min(j0 + batch, iters))
+                    so = np.stack([shuffled_ids(t, int(ss[jj])) for jj in jr])
+                    bo = np.stack([shuffled_ids(nb, int(bs[jj])) for jj in jr])
+                    res = ctx.batch_scan(L.SITEBOND, site_orders=so, bond_orders=bo, scan=scan, fixed=fx)
+                    for jj, r in zip(jr, res):
+                        first = r["first"]
+                        if scan == L.BOND:
+                            ps = float(np.float32(fx) / np.float32(t))
+                            pb = float(np.float32(first) / np.float32(nb)) if first else 0.0
+                        else:
+                            pb = float(np.float32(fx) / np.float32(nb))
+                            ps = float(np.float32(first) / np.float32(t)) if first else 0.0
+                        out.append(dict(sseed=int(ss[jj]), bseed=int(bs[jj]), ps=ps, pb=pb, first=first))
+            return out
         for ii, pt in enumerate(points):
             ss, bs = paired_seeds(pseed[ii])
             for jj in range(iters):

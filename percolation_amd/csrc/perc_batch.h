@@ -59,6 +59,42 @@ int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders);
 int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
                     const int* item_count, int solve, bool replay, double Va, double g0, double leak,
                     int itol, double tol, int itmax, perc_batch_item* out);
+// ---- threshold scans (perc_batch_scan.hip: k_batch_scan) ----------------
+// sites of the largest lattice one workgroup scans (128 x 128)
+constexpr int kScanSites = 16384;
+constexpr int kScanSPT = 16;  // sites per thread, at most
+// Byte offsets of k_batch_scan's LDS arena (every offset a multiple of 16):
+// parent (int, t + 1) at 0, the per-root sizes (int, t + 1; the site
+// occupancy while the links of a labeling are formed), one link byte per site
+// (bit k: the forward bond to nearestn slot k connects; bit 7: member site),
+// the spanning flags (m + 1 bytes), 16 ints.
+struct ScanLds {
+  int oSize, oLink, oFlag, oInt, total;
+};
+ScanLds scan_lds(const Geom& g);
+constexpr int kScanLdsStatic = 256;  // the compiler's own static LDS of k_batch_scan (resource usage)
+// threads per workgroup for t sites: the fewest of 256 / 512 / 1024 that keep
+// kScanSPT sites per thread
+int scan_threads(int t);
+// host-only check of perc_scan_supported
+bool scan_supported(const Geom& g);
+// device side.  Scan of ntrials trials from rank arrays in device memory
+// (d_rank_b: ntrials x nb as dev_batch_upload leaves them, d_rank_s: ntrials
+// x t; either may be NULL where the kind does not read it); fixed (host,
+// ntrials, mixed kinds only); out (host, ntrials).  kind PERC_BOND /
+// PERC_SITE / PERC_SITEBOND, scan PERC_BOND / PERC_SITE (mixed only).
+hipError_t dev_scan_run(perc_ctx* h, int kind, int scan, int ntrials, const int* d_rank_s,
+                        const int* d_rank_b, const int* fixed, perc_scan_item* out);
+// rank arrays of perc_batch_scan's own orders (host, ntrials x t / ntrials x
+// nb, either NULL) uploaded into the scan's buffers, then dev_scan_run
+hipError_t dev_scan_upload_run(perc_ctx* h, int kind, int scan, int ntrials, const int* rank_s,
+                               const int* rank_b, const int* fixed, perc_scan_item* out);
+void dev_scan_free(perc_ctx* h);
+// the rank arrays dev_batch_upload left on the device (NULL before one)
+const int* dev_batch_ranks(perc_ctx* h, int* ntrials);
+// host side (perc_batch_host.cpp): the first spanning bond count of every
+// trial of the group batch_upload_orders uploaded (bond kind), one launch
+int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out);
 // the closed-form rows' forms of the square lattice (perc_assemble.hip)
 void asm_closed_forms(perc_ctx* h, int* fast_out, int* fl_out, int* fr_out);
 

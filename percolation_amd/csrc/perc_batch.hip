@@ -9,6 +9,7 @@
 
 #include "perc_asm_row.h"
 #include "perc_batch.h"
+#include "perc_batch_uf.h"
 
 namespace perc {
 namespace {
@@ -29,16 +30,6 @@ struct BatchArgs {
   double Va, g0, leak, tol;
   BatchLds L;
 };
-
-// root of x (parents only decrease along a chain; hooks of other threads may
-// land while it is walked: every value read is an ancestor at some moment)
-__device__ __forceinline__ int lds_find(int* parent, int x) {
-  while (true) {
-    const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (p == x) return x;
-    x = p;
-  }
-}
 
 // NT threads, rows t, t + NT, .. (at most kBatchEPT) per thread.  LIT: the
 // literal dot order (wave 0 folds every sum in ascending j, fold_chunk) --
@@ -88,40 +79,15 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
   load_forms(*a.forms, s_off);  // (ends with a workgroup barrier)
 
   // ---- labeling: hook the larger root under the smaller over every occupied
-  // bond, flatten, until a pass hooks nothing (the flag is workgroup-uniform)
-  for (int pass = 0;; ++pass) {
-    int changed = 0;
-    for (int s = t + 1; s < T; s += NT) {
-      const int sr = div_m(g, s - 1);
-      int nn[6];
-      nearestn_rc(g, s, sr, s - 1 - sr * m, nn);
-      int id = a.bond_first[s];
-      for (int k = 0; k < g.scn; ++k) {
-        const int q = nn[k];
-        if (q <= s) continue;
-        if (bocc[id]) {
-          if (pass == 0) {
-            member[s] = 1;
-            member[q] = 1;
-          }
-          const int ra = lds_find(parent, s), rb = lds_find(parent, q);
-          if (ra != rb) {
-            atomicMin(&parent[max(ra, rb)], min(ra, rb));
-            changed = 1;
-          }
-        }
-        ++id;
-      }
+  // bond, flatten, until a pass hooks nothing (lds_label)
+  lds_label<NT>(g, a.bond_first, parent, [&](int pass, int s, int, int q, int id) {
+    if (!bocc[id]) return false;
+    if (pass == 0) {
+      member[s] = 1;
+      member[q] = 1;
     }
-    changed = __syncthreads_or(changed);
-    // each thread walks, then writes only its own entries
-    for (int s = t + 1; s <= T; s += NT) {
-      const int r = lds_find(parent, s);
-      __hip_atomic_store(&parent[s], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __syncthreads();
-    if (!changed) break;
-  }
+    return true;
+  });
 
   // ---- spanning (k_span_top's rule): root <= m and a top-row member
   for (int c = t; c < m; c += NT) {
@@ -457,6 +423,12 @@ void dev_batch_free(perc_ctx* h) {
   (void)hipFree(B->d_sflag);
   delete B;
   h->batch = nullptr;
+}
+
+const int* dev_batch_ranks(perc_ctx* h, int* ntrials) {
+  BatchState* B = static_cast<BatchState*>(h->batch);
+  *ntrials = B ? B->ntrials : 0;
+  return B ? B->d_rank : nullptr;
 }
 
 hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank) {

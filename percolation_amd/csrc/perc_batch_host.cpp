@@ -1,7 +1,8 @@
 // perc_batch_host.cpp -- host side of the batch path (include/perc.h:
-// perc_batch_supported, perc_batch_bondc): argument checks, the orders'
-// inverse permutations, the launch geometry, the fold of the terminal
-// currents and the single-path replay of the items several clusters span.
+// perc_batch_supported, perc_batch_bondc, perc_scan_supported,
+// perc_batch_scan): argument checks, the orders' inverse permutations, the
+// launch geometry and LDS layouts, the fold of the terminal currents and the
+// single-path replay of the items several clusters span.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -78,20 +79,43 @@ bool batch_supported(const Geom& g) {
   return L.total + kBatchLdsStatic <= kBatchLdsMax;
 }
 
+ScanLds scan_lds(const Geom& g) {
+  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
+  ScanLds L{};
+  L.oSize = up16(4 * ((long long)g.t + 1));
+  L.oLink = L.oSize + up16(4 * ((long long)g.t + 1));
+  L.oFlag = L.oLink + up16((long long)g.t + 1);
+  L.oInt = L.oFlag + up16((long long)g.m + 1);
+  L.total = L.oInt + 64;
+  return L;
+}
+
+int scan_threads(int t) { return t <= 256 * kScanSPT ? 256 : (t <= 512 * kScanSPT ? 512 : 1024); }
+
+bool scan_supported(const Geom& g) {
+  if (g.n < 3 || g.m < 3 || (long long)g.m * g.n > kScanSites) return false;
+  return scan_lds(g).total + kScanLdsStatic <= kBatchLdsMax;
+}
+
+// rank[tr * N + id - 1] = position of id in trial tr's order of N + 1 entries
+// (the spill slot 0 takes a position and is no element; INT_MAX: absent)
+static void order_ranks(int ntrials, int N, const int* orders, int* rank) {
+  std::fill(rank, rank + (size_t)ntrials * N, INT_MAX);
+  for (int tr = 0; tr < ntrials; ++tr) {
+    const int* o = orders + (size_t)tr * (N + 1);
+    int* r = rank + (size_t)tr * N;
+    for (int pos = 0; pos <= N; ++pos) {
+      const int id = o[pos];
+      if (id >= 1 && id <= N && r[id - 1] == INT_MAX) r[id - 1] = pos;
+    }
+  }
+}
+
 int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders) {
   const int nb = (int)h->nb;
   hipSetDevice(h->device);
-  // rank[id - 1] = position of bond id in the order (the spill slot 0 takes a
-  // position and is no bond)
-  std::vector<int> rank((size_t)ntrials * nb, INT_MAX);
-  for (int tr = 0; tr < ntrials; ++tr) {
-    const int* o = orders + (size_t)tr * (nb + 1);
-    int* r = rank.data() + (size_t)tr * nb;
-    for (int pos = 0; pos <= nb; ++pos) {
-      const int id = o[pos];
-      if (id >= 1 && id <= nb && r[id - 1] == INT_MAX) r[id - 1] = pos;
-    }
-  }
+  std::vector<int> rank((size_t)ntrials * nb);
+  order_ranks(ntrials, nb, orders, rank.data());
   hipError_t e = dev_batch_upload(h, ntrials, rank.data());
   if (e != hipSuccess) return hip_status(e, "perc_batch_bondc/upload");
   return PERC_OK;
@@ -176,6 +200,18 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
   return PERC_OK;
 }
 
+int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out) {
+  hipSetDevice(h->device);
+  int have = 0;
+  const int* d_rank = dev_batch_ranks(h, &have);
+  if (!d_rank || have < ntrials) {
+    set_error("batch_scan_uploaded: no uploaded group of that many trials");
+    return PERC_ESTATE;
+  }
+  return hip_status(dev_scan_run(h, PERC_BOND, PERC_BOND, ntrials, nullptr, d_rank, nullptr, out),
+                    "perc_batch_scan");
+}
+
 }  // namespace perc
 
 using namespace perc;
@@ -213,6 +249,67 @@ int perc_batch_bondc(perc_ctx* h, int ntrials, const int* orders, int nitems, co
   if (rc) return rc;
   return batch_run_items(h, orders, nitems, item_trial, item_count, solve, true, Va, g0, leak, itol,
                          tol, itmax, out);
+}
+
+int perc_scan_supported(int lattice, int m, int n, int pbc) {
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n > kScanSites) return 0;
+  return scan_supported(make_geom(lattice, m, n, pbc)) ? 1 : 0;
+}
+
+int perc_batch_scan(perc_ctx* h, int kind, int scan, int ntrials, const int* site_orders,
+                    const int* bond_orders, const int* fixed, perc_scan_item* out) {
+  if (!h) return PERC_EINVAL;
+  if (!scan_supported(h->g)) {
+    set_error("perc_batch_scan: lattice not supported by the scan kernel (perc_scan_supported)");
+    return PERC_EINVAL;
+  }
+  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND) {
+    set_error("perc_batch_scan: kind PERC_BOND, PERC_SITE or PERC_SITEBOND only");
+    return PERC_EINVAL;
+  }
+  if (kind == PERC_SITEBOND && scan != PERC_BOND && scan != PERC_SITE) {
+    set_error("perc_batch_scan: scan PERC_BOND or PERC_SITE only");
+    return PERC_EINVAL;
+  }
+  if (ntrials < 0) {
+    set_error("perc_batch_scan: ntrials < 0");
+    return PERC_EINVAL;
+  }
+  if (ntrials == 0) return PERC_OK;
+  const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
+  if ((need_s && !site_orders) || (need_b && !bond_orders) || !out) {
+    set_error("perc_batch_scan: an order list the kind reads (or out) is missing");
+    return PERC_EINVAL;
+  }
+  const int t = h->g.t, nb = (int)h->nb;
+  if (kind == PERC_SITEBOND) {
+    if (!fixed) {
+      set_error("perc_batch_scan: PERC_SITEBOND needs fixed[ntrials]");
+      return PERC_EINVAL;
+    }
+    const int cap = scan == PERC_BOND ? t : nb;
+    for (int i = 0; i < ntrials; ++i)
+      if (fixed[i] < 0 || fixed[i] > cap) {
+        set_error("perc_batch_scan: fixed outside 0..t (scan PERC_BOND) / 0..nb (scan PERC_SITE)");
+        return PERC_EINVAL;
+      }
+  }
+  hipSetDevice(h->device);
+  // launches whose rank arrays stay under 64 MB of device memory
+  const long long per = 4LL * ((need_s ? t : 0) + (need_b ? nb : 0));
+  const int chunk = (int)std::max(1LL, std::min<long long>(ntrials, (64LL << 20) / per));
+  std::vector<int> rank_s(need_s ? (size_t)chunk * t : 0), rank_b(need_b ? (size_t)chunk * nb : 0);
+  for (int i0 = 0; i0 < ntrials; i0 += chunk) {
+    const int k = std::min(chunk, ntrials - i0);
+    if (need_s) order_ranks(k, t, site_orders + (size_t)i0 * (t + 1), rank_s.data());
+    if (need_b) order_ranks(k, nb, bond_orders + (size_t)i0 * (nb + 1), rank_b.data());
+    const hipError_t e = dev_scan_upload_run(h, kind, scan, k, need_s ? rank_s.data() : nullptr,
+                                             need_b ? rank_b.data() : nullptr,
+                                             kind == PERC_SITEBOND ? fixed + i0 : nullptr, out + i0);
+    if (e != hipSuccess) return hip_status(e, "perc_batch_scan");
+  }
+  return PERC_OK;
 }
 
 }  // extern "C"

@@ -244,9 +244,9 @@ int perc_ensemble_allreduce(perc_ensemble* e, double* stats, int k) {
 // perc_ensemble_bond_cond with the batch path on: per device one host thread
 // takes its trials in groups of about `items` grid-point realisations.  A
 // group's orders are shuffled on the host and uploaded once (as rank arrays);
-// one launch solves every (trial, grid point) of the group, then the first
-// spanning count of every trial is bisected with one label-only launch over
-// the group per step, and perccln comes from the host replay.  Same stop
+// one launch solves every (trial, grid point) of the group, a second one
+// bisects the first spanning count of every trial (k_batch_scan over the
+// same rank arrays), and perccln comes from the host replay.  Same stop
 // rules, outputs and statistics (accumulated in ascending trial order) as
 // the per-trial loop.
 static int bond_cond_batched(perc_ensemble* e, int ntrials, const int* tseed, int npts,
@@ -272,6 +272,7 @@ static int bond_cond_batched(perc_ensemble* e, int ntrials, const int* tseed, in
     double* a = acc.data() + (size_t)d * npts * 5;
     std::vector<int> trials, orders, it_tr, it_cnt, lo, hi;
     std::vector<perc_batch_item> out;
+    std::vector<perc_scan_item> scan;
     auto fail = [&](int rc) {
       rcs[d] = rc;
       errs[d] = perc_last_error();
@@ -314,33 +315,43 @@ static int bond_cond_batched(perc_ensemble* e, int ntrials, const int* tseed, in
         }
         nrows[t] = R;
       }
-      // pc (bond_cond.f:353-389): spanning with every bond, then the
-      // bisection of perc_first_spanning, a label-only launch per step
-      it_tr.resize(g);
-      it_cnt.assign(g, nb);
-      for (int k = 0; k < g; ++k) it_tr[k] = k;
-      rc = batch_run_items(h, orders.data(), g, it_tr.data(), it_cnt.data(), 0, false, Va, g0, 1.0e-12,
-                           2, tol, itmax, out.data());
-      if (rc) return fail(rc);
-      lo.assign(g, 0);
+      // pc (bond_cond.f:353-389): the bisection of perc_first_spanning for
+      // every trial of the group in one launch over the uploaded rank arrays
+      // (k_batch_scan: one workgroup bisects each trial)
       hi.assign(g, 0);
-      for (int k = 0; k < g; ++k) hi[k] = out[k].nspan > 0 ? nb : 0;
-      while (true) {
-        it_tr.clear();
-        it_cnt.clear();
-        for (int k = 0; k < g; ++k)
-          if (hi[k] - lo[k] > 1) {
-            it_tr.push_back(k);
-            it_cnt.push_back(lo[k] + (hi[k] - lo[k]) / 2);
-          }
-        if (it_tr.empty()) break;
-        rc = batch_run_items(h, orders.data(), (int)it_tr.size(), it_tr.data(), it_cnt.data(), 0, false,
-                             Va, g0, 1.0e-12, 2, tol, itmax, out.data());
+      if (scan_supported(h->g)) {
+        scan.resize(g);
+        rc = batch_scan_uploaded(h, g, scan.data());
         if (rc) return fail(rc);
-        for (size_t i = 0; i < it_tr.size(); ++i) {
-          const int k = it_tr[i];
-          if (out[i].nspan > 0) hi[k] = it_cnt[i];
-          else lo[k] = it_cnt[i];
+        for (int k = 0; k < g; ++k) hi[k] = scan[k].first;
+      } else {
+        // (3 rows of more than 5461 sites: past the scan kernel's arena) a
+        // label-only launch over the group per step
+        it_tr.resize(g);
+        it_cnt.assign(g, nb);
+        for (int k = 0; k < g; ++k) it_tr[k] = k;
+        rc = batch_run_items(h, orders.data(), g, it_tr.data(), it_cnt.data(), 0, false, Va, g0, 1.0e-12,
+                             2, tol, itmax, out.data());
+        if (rc) return fail(rc);
+        lo.assign(g, 0);
+        for (int k = 0; k < g; ++k) hi[k] = out[k].nspan > 0 ? nb : 0;
+        while (true) {
+          it_tr.clear();
+          it_cnt.clear();
+          for (int k = 0; k < g; ++k)
+            if (hi[k] - lo[k] > 1) {
+              it_tr.push_back(k);
+              it_cnt.push_back(lo[k] + (hi[k] - lo[k]) / 2);
+            }
+          if (it_tr.empty()) break;
+          rc = batch_run_items(h, orders.data(), (int)it_tr.size(), it_tr.data(), it_cnt.data(), 0, false,
+                               Va, g0, 1.0e-12, 2, tol, itmax, out.data());
+          if (rc) return fail(rc);
+          for (size_t i = 0; i < it_tr.size(); ++i) {
+            const int k = it_tr[i];
+            if (out[i].nspan > 0) hi[k] = it_cnt[i];
+            else lo[k] = it_cnt[i];
+          }
         }
       }
       for (int k = 0; k < g; ++k) {

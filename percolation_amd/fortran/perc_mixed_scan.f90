@@ -14,11 +14,17 @@
 !            (as_built = .true., default) or, as_built = .false., the
 !            intended site+bond connectivity on the GPU.
 !
+! With batch > 0 (on a lattice perc_scan_supported accepts; not for the
+! as-built bs_perc, a host replay) the GPU bisections of `batch` trials at a
+! time run in one perc_batch_scan call, one workgroup each; the records and
+! the stdout lines are the same, in trial order.  batch = 0 (default): one
+! perc_first_spanning_mixed call per trial.
+!
 ! Parameters: the reference's blocks (sb: 50x50, seed 8811064, ps 0.59 +
 ! 0.01 i x 42 (triangular 0.50 + 0.01 i x 51), iter 100; bs: 10x10, seed
 ! 229102, pb 0.30 + 0.01 i x 71, iter 1000), overridable by sb_perc.nml /
 ! bs_perc.nml (&mixed_scan_nml lattice, m, n, pbc, seed, pstart, pstep,
-! npoints, iters, as_built, device /).
+! npoints, iters, as_built, device, batch /).
 program perc_mixed_scan
   use perc_api
   implicit none
@@ -28,13 +34,16 @@ program perc_mixed_scan
 #ifndef PERC_SCAN_BS
 #define PERC_SCAN_BS 0
 #endif
-  integer(c_int) :: lattice, m, n, pbc, seed, npoints, iters, device
+  integer(c_int) :: lattice, m, n, pbc, seed, npoints, iters, device, batch
   double precision :: pstart, pstep
   logical :: as_built
   namelist /mixed_scan_nml/ lattice, m, n, pbc, seed, pstart, pstep, npoints, iters, as_built, &
-                            device
+                            device, batch
   integer(c_int) :: t, nb, ii, jj, fixed, first, pseed(100), sseed(1000), bseed(1000)
-  integer(c_int), allocatable, target :: sorder(:), border(:)
+  integer(c_int) :: j0, k, g, scan
+  integer(c_int), allocatable, target :: sorder(:), border(:), sorders(:, :), borders(:, :), fx(:)
+  type(perc_scan_item), allocatable, target :: items(:)
+  logical :: batched
   double precision :: pt, ps, pb
   character(len=16) :: nml, out
   type(c_ptr) :: h
@@ -44,6 +53,7 @@ program perc_mixed_scan
   pbc = 0
   as_built = .true.
   device = 0
+  batch = 0
   if (PERC_SCAN_BS == 1) then
     m = 10
     n = 10
@@ -84,6 +94,12 @@ program perc_mixed_scan
   call perc_trial_seeds(seed, 100, pseed)
   call perc_check(perc_ctx_create(device, lattice, m, n, pbc, h), 'perc_ctx_create')
   open(unit=10, file=trim(out))
+  batched = batch > 0 .and. .not. (PERC_SCAN_BS == 1 .and. as_built)
+  if (batched) batched = perc_scan_supported(lattice, m, n, pbc) == 1
+  if (batched) then
+    g = min(batch, iters)
+    allocate(sorders(t + 1, g), borders(nb + 1, g), fx(g), items(g))
+  end if
   do ii = 1, npoints
     pt = pstart + (pstep * (ii - 1))
     call perc_srand(pseed(ii))
@@ -91,6 +107,40 @@ program perc_mixed_scan
       sseed(jj) = int(perc_rand(0) * 10000000) + 1
       bseed(jj) = int(perc_rand(0) * 10000000) + 1
     end do
+    if (batched) then
+      if (PERC_SCAN_BS == 1) then
+        scan = PERC_SITE
+        fixed = pt * nb
+      else
+        scan = PERC_BOND
+        fixed = pt * t
+      end if
+      fx = fixed
+      do j0 = 1, iters, g
+        k = min(g, iters - j0 + 1)
+        do jj = 1, k
+          call perc_shuffled_ids(t, sseed(j0 + jj - 1), sorders(:, jj))
+          call perc_shuffled_ids(nb, bseed(j0 + jj - 1), borders(:, jj))
+        end do
+        call perc_check(perc_batch_scan(h, PERC_SITEBOND, scan, k, c_loc(sorders), c_loc(borders), &
+                        c_loc(fx), c_loc(items)), 'perc_batch_scan')
+        do jj = 1, k
+          first = items(jj)%first
+          if (PERC_SCAN_BS == 1) then
+            pb = real(fixed) / real(nb)
+            ps = 0.00d+00
+            if (first > 0) ps = real(first) / real(t)
+          else
+            ps = real(fixed) / real(t)
+            pb = 0.00d+00
+            if (first > 0) pb = real(first) / real(nb)
+          end if
+          write(6, 111) sseed(j0 + jj - 1), bseed(j0 + jj - 1), ps, pb
+          write(10, 111) sseed(j0 + jj - 1), bseed(j0 + jj - 1), ps, pb
+        end do
+      end do
+      cycle
+    end if
     do jj = 1, iters
       call perc_shuffled_ids(t, sseed(jj), sorder)
       call perc_shuffled_ids(nb, bseed(jj), border)

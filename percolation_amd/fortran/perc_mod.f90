@@ -30,6 +30,11 @@ module perc_api
     integer(c_int) :: nclusters, nspan, span_root, span_sites, replayed, perccln
   end type perc_label_info
 
+  ! one trial of perc_batch_scan
+  type, bind(C) :: perc_scan_item
+    integer(c_int) :: first, maxcs, span_size, nspan
+  end type perc_scan_item
+
   type, bind(C) :: perc_cond_result
     real(c_double) :: gtop, gbot, err
     integer(c_int) :: iter, status
@@ -292,6 +297,23 @@ module perc_api
       import :: c_int
       integer(c_int), value :: lattice, m, n, pbc
     end function perc_batch_supported
+
+    ! host-only: 1 when the scan kernel can run this lattice
+    integer(c_int) function perc_scan_supported(lattice, m, n, pbc) &
+        bind(C, name='perc_scan_supported')
+      import :: c_int
+      integer(c_int), value :: lattice, m, n, pbc
+    end function perc_scan_supported
+
+    ! many threshold-scan trials in one launch, one workgroup bisecting each;
+    ! site_orders(t + 1, ntrials), bond_orders(nb + 1, ntrials), fixed(ntrials),
+    ! out(ntrials): pointers so that unused ones can be c_null_ptr
+    integer(c_int) function perc_batch_scan(h, kind, scan, ntrials, site_orders, bond_orders, &
+        fixed, out) bind(C, name='perc_batch_scan')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h, site_orders, bond_orders, fixed, out
+      integer(c_int), value :: kind, scan, ntrials
+    end function perc_batch_scan
 
     integer(c_int) function perc_ensemble_bond_cond(e, ntrials, tseed, npts, nbarr, Va, g0, &
         tol, itmax, nrows, gbot, gtop, iters, bf_c, perccln, stats) &

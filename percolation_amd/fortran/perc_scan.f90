@@ -12,9 +12,15 @@
 ! that count from perc_cluster_sizes (GPU; equal to the reference's c(label)
 ! of the largest and of the spanning cluster, tests/test_threshold_scan.py).
 !
+! With batch > 0 (on a lattice perc_scan_supported accepts) the orders of
+! `batch` trials at a time are shuffled on the host and one perc_batch_scan
+! call bisects them all, one workgroup each; the records and the stdout
+! lines are the same, in trial order.  batch = 0 (default): the loop above.
+!
 ! Parameters: the reference's block (50x50, numtrials 10 for bond_perc /
 ! 1000 for site_perc, master seed 58302), overridable by bond_perc.nml /
-! site_perc.nml (&perc_scan_nml lattice, m, n, pbc, numtrials, seed, device /).
+! site_perc.nml (&perc_scan_nml lattice, m, n, pbc, numtrials, seed, device,
+! batch /).
 program perc_scan
   use perc_api
   implicit none
@@ -24,10 +30,12 @@ program perc_scan
 #ifndef PERC_SCAN_SITE
 #define PERC_SCAN_SITE 0
 #endif
-  integer(c_int) :: lattice, m, n, pbc, numtrials, seed, device
-  namelist /perc_scan_nml/ lattice, m, n, pbc, numtrials, seed, device
-  integer(c_int) :: kind, nn, ii, first, cnt, perccls, maxcs, spansz
-  integer(c_int), allocatable, target :: tseed(:), order(:)
+  integer(c_int) :: lattice, m, n, pbc, numtrials, seed, device, batch
+  namelist /perc_scan_nml/ lattice, m, n, pbc, numtrials, seed, device, batch
+  integer(c_int) :: kind, nn, ii, first, cnt, perccls, maxcs, spansz, i0, k, g
+  integer(c_int), allocatable, target :: tseed(:), order(:), orders(:, :)
+  type(perc_scan_item), allocatable, target :: items(:)
+  type(c_ptr) :: sp, bp
   character(len=16) :: nml, out
   real :: f
   type(c_ptr) :: h
@@ -39,6 +47,7 @@ program perc_scan
   pbc = 0
   seed = 58302
   device = 0
+  batch = 0
   if (PERC_SCAN_SITE == 1) then
     kind = PERC_SITE
     numtrials = 1000
@@ -66,6 +75,36 @@ program perc_scan
   call perc_trial_seeds_scaled(seed, numtrials, 1000000, tseed)
   call perc_check(perc_ctx_create(device, lattice, m, n, pbc, h), 'perc_ctx_create')
   open(unit=10, file=trim(out))
+  if (batch > 0 .and. perc_scan_supported(lattice, m, n, pbc) == 1) then
+    g = min(batch, numtrials)
+    allocate(orders(nn + 1, g), items(g))
+    sp = c_null_ptr
+    bp = c_null_ptr
+    if (kind == PERC_BOND) then
+      bp = c_loc(orders)
+    else
+      sp = c_loc(orders)
+    end if
+    do i0 = 1, numtrials, g
+      k = min(g, numtrials - i0 + 1)
+      do ii = 1, k
+        call perc_shuffled_ids(nn, tseed(i0 + ii - 1), orders(:, ii))
+      end do
+      call perc_check(perc_batch_scan(h, kind, PERC_BOND, k, sp, bp, c_null_ptr, c_loc(items)), &
+                      'perc_batch_scan')
+      do ii = 1, k
+        cnt = items(ii)%first
+        if (cnt == 0) cnt = nn
+        maxcs = items(ii)%maxcs
+        perccls = 0
+        if (items(ii)%first > 0) perccls = items(ii)%span_size
+        f = real(cnt) / real(nn)
+        write(6, *) tseed(i0 + ii - 1), f, maxcs, perccls
+        write(10, 111) tseed(i0 + ii - 1), f, maxcs, perccls
+      end do
+    end do
+    numtrials = 0  ! (every trial done)
+  end if
   do ii = 1, numtrials
     call perc_shuffled_ids(nn, tseed(ii), order)
     call perc_check(perc_first_spanning(h, kind, c_loc(order), nn, 0, first), &

@@ -12,6 +12,16 @@
 Prints one JSON line per workload: trials/s and the per-trial split.
 
   python tools/scan_bench.py [--L 256,1024 --trials 8 --cond-L 64,256 --cond-trials 2]
+
+With --batch N (lattices perc_scan_supported accepts) each bond_perc /
+site_perc workload is timed twice in the same process, the shuffles
+included, --reps times in alternation: the per-trial path above and the
+batch path (the orders of N trials at a time shuffled on the host, one
+perc_batch_scan call per group: one workgroup bisects each trial).  Prints
+both trials/s (medians), their ratio and whether the two paths' records agree;
+bond_cond is not run.
+
+  python tools/scan_bench.py --L 50 --trials 1000 --batch 256
 """
 import argparse
 import json
@@ -56,6 +66,56 @@ def scan(api, L_mod, lat, L_, kind, trials):
                 mean_first_fraction=round(float(np.mean(firsts)) / N, 5))
 
 
+def scan_ab(api, L_mod, lat, L_, kind, trials, batch, reps):
+    """the per-trial path and the batch path on the same trials, alternating"""
+    N = api.nbonds(lat, L_, L_, 0) if kind == L_mod.BOND else L_ * L_
+    seeds = api.trial_seeds(58302, trials, scale=1000000)
+    key = "bond_orders" if kind == L_mod.BOND else "site_orders"
+
+    def per_trial(ctx):
+        out = []
+        for ii in range(trials):
+            order = api.shuffled_ids(N, int(seeds[ii]))
+            first = api.first_spanning(ctx, order, kind, N)
+            out.append((first,) + ctx.cluster_sizes())
+        return out
+
+    def batched(ctx):
+        out, t_shuf = [], 0.0
+        for i0 in range(0, trials, batch):
+            a = time.perf_counter()
+            orders = np.stack([api.shuffled_ids(N, int(s)) for s in seeds[i0:i0 + batch]])
+            t_shuf += time.perf_counter() - a
+            out += [(r["first"], r["maxcs"], r["span_size"]) for r in ctx.batch_scan(kind, **{key: orders})]
+        return out, t_shuf
+
+    with api.Context(lat, L_, L_, 0) as ctx:
+        warm = api.shuffled_ids(N, 12345)
+        api.first_spanning(ctx, warm, kind, N)  # warm-up of both paths
+        ctx.cluster_sizes()
+        ctx.batch_scan(kind, **{key: np.stack([warm] * min(batch, trials))})
+        ta, tb, ts = [], [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            ra = per_trial(ctx)
+            t1 = time.perf_counter()
+            rb, shuf = batched(ctx)
+            t2 = time.perf_counter()
+            ta.append(t1 - t0)
+            tb.append(t2 - t1)
+            ts.append(shuf)
+    wa, wb = float(np.median(ta)), float(np.median(tb))
+    return dict(workload="%s_perc %s L=%d" % ("bond" if kind == L_mod.BOND else "site",
+                                               "square" if lat == 0 else "triangular", L_),
+                trials=trials, batch=batch, reps=reps,
+                per_trial_trials_per_s=round(trials / wa, 2), batch_trials_per_s=round(trials / wb, 2),
+                ratio=round(wa / wb, 2),
+                per_trial_s=[round(x, 4) for x in ta], batch_s=[round(x, 4) for x in tb],
+                batch_host_shuffle_s=round(float(np.median(ts)), 4),
+                records_equal=ra == rb,
+                mean_first_fraction=round(float(np.mean([r[0] for r in rb])) / N, 5))
+
+
 def cond(api, lat, L_, trials):
     with api.Context(lat, L_, L_, 0) as ctx:
         api.bond_cond_grid(lat, L_, L_, 0, numtrials=1, itmax=10 ** 6, ctx=ctx)  # warm-up
@@ -77,9 +137,20 @@ def main():
     ap.add_argument("--trials", type=int, default=8)
     ap.add_argument("--cond-L", default="64,256")
     ap.add_argument("--cond-trials", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=0,
+                    help="A/B of the per-trial path and perc_batch_scan with this many trials per call")
+    ap.add_argument("--reps", type=int, default=3, help="alternating repetitions of the A/B")
     args = ap.parse_args()
     from percolation_amd import _lib as L_mod
     from percolation_amd import api
+    if args.batch > 0:
+        for L_ in map(int, args.L.split(",")):
+            if not api.scan_supported(0, L_, L_, 0):
+                raise SystemExit("L=%d: not a lattice perc_scan_supported accepts" % L_)
+            for kind in (L_mod.BOND, L_mod.SITE):
+                print(json.dumps(scan_ab(api, L_mod, 0, L_, kind, args.trials, args.batch,
+                                         args.reps)), flush=True)
+        return
     for L_ in map(int, args.L.split(",")):
         for kind in (L_mod.BOND, L_mod.SITE):
             print(json.dumps(scan(api, L_mod, 0, L_, kind, args.trials)), flush=True)

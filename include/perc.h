@@ -622,6 +622,53 @@ int perc_batch_bondc(perc_ctx *h, int ntrials, const int *orders /* ntrials x (n
                      double Va, double g0, double leak, int itol, double tol, int itmax,
                      perc_batch_item *out);
 
+/* ---- the same for site and mixed conductance --------------------------- *
+ * site.f / sitebond.f with ConductCalc.m's site rule (:88-109) and mixed
+ * rule (:134-160) on the reference's 10 x 10 .. 50 x 50 lattices: the other
+ * two (kind, rule) pairs through the same one-workgroup kernel.
+ *   kind PERC_BOND,     rule PERC_RULE_BOND   bond id occupied iff its position
+ *                       in the trial's bond order < item_nbonds[i]; a bond
+ *                       connects iff it is occupied (perc_batch_bondc's items)
+ *   kind PERC_SITE,     rule PERC_RULE_SITE   site occupied iff its position in
+ *                       the trial's site order < item_nsites[i]; a bond
+ *                       connects iff both end sites are occupied
+ *   kind PERC_SITEBOND, rule PERC_RULE_MIXED  both lists; a bond connects iff it
+ *                       and both end sites are occupied
+ * Item i is the first item_nsites[i] sites and item_nbonds[i] bonds of trial
+ * item_trial[i]'s orders (site_orders: ntrials rows of t + 1 entries,
+ * bond_orders: ntrials rows of nb + 1, as perc_shuffle leaves them; the spill
+ * slot 0 takes a position and is no element; a count of t + 1 / nb + 1 is
+ * the whole order).  The list the kind does not read may be NULL.  Labels
+ * are perc_label's: an isolated occupied site of the site and mixed kinds is
+ * a cluster of its own in nclusters.  cur_rule PERC_CUR_FORTRAN or
+ * PERC_CUR_MATLAB, as perc_conductance.  solve, the dot order (literal
+ * results are bitwise perc_conductance's under PERC_DOT_LITERAL), itol 1 or
+ * 2 and the out record are perc_batch_bondc's; with kind PERC_BOND and
+ * PERC_CUR_FORTRAN the results are perc_batch_bondc's own.  When several
+ * clusters span (nspan > 1) the item comes back with fallback = 1, filled by
+ * perc_occupy(kind, ..) / perc_label / perc_conductance(rule, cur_rule, ..)
+ * on the context, the spill slot dropped where a count covers a whole order.
+ * The context's single-realisation state (occupancy, labeling, assembled
+ * system) is therefore what the last fallback item left; without one it is
+ * unchanged.  nitems == 0 is PERC_OK.  PERC_EINVAL (text in
+ * perc_last_error): a (kind, rule) pair outside the table, a cur_rule other
+ * than the two, itol 3 / 4, a lattice perc_batch_cond_supported refuses for
+ * the kind, a missing order list or count list the kind reads, item_trial
+ * outside 0..ntrials-1, item_nsites outside 0..t+1, item_nbonds outside
+ * 0..nb+1, ntrials or nitems below 0. */
+/* host-only: 1 when the batch kernel can run this kind on this lattice:
+   perc_batch_supported for PERC_BOND; for PERC_SITE / PERC_SITEBOND the same
+   checks with the kind's own LDS layout (one more byte per site) */
+int perc_batch_cond_supported(int kind, int lattice, int m, int n, int pbc);
+int perc_batch_cond(perc_ctx *h, int kind, int rule, int cur_rule, int ntrials,
+                    const int *site_orders /* ntrials x (t+1), NULL for PERC_BOND */,
+                    const int *bond_orders /* ntrials x (nb+1), NULL for PERC_SITE */,
+                    int nitems, const int *item_trial,
+                    const int *item_nsites /* NULL for PERC_BOND */,
+                    const int *item_nbonds /* NULL for PERC_SITE */,
+                    int solve, double Va, double g0, double leak, int itol,
+                    double tol, int itmax, perc_batch_item *out);
+
 /* ---- batch of small threshold scans (one workgroup each) -------------- *
  * The reference's threshold programs (Fortran/Square/bond_perc.f:204-366,
  * site_perc.f:150-256, sb_perc.f:104-372, bs_perc.f:104-395) are ensembles

@@ -184,6 +184,10 @@ SIGNATURES = {
     "perc_batch_supported": (C.c_int, [C.c_int] * 4),
     "perc_batch_bondc": (C.c_int, [_VP, C.c_int, _I, C.c_int, _I, _I, C.c_int, C.c_double,
                                    C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _VP]),
+    "perc_batch_cond_supported": (C.c_int, [C.c_int] * 5),
+    "perc_batch_cond": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP,
+                                  _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                  C.c_double, C.c_int, _VP]),
     "perc_scan_supported": (C.c_int, [C.c_int] * 4),
     "perc_batch_scan": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
     "perc_ensemble_ctx": (C.c_void_p, [_VP, C.c_int]),

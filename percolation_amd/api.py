@@ -8,6 +8,9 @@ parameter names and semantics:
   site       Fortran/*/site.f (+ MATLAB/ConductCalc.m site rule)
   sitebond   Fortran/*/sitebond.f (+ ConductCalc.m mixed rule)
   bond_cond  Fortran/*/bond_cond.f grid-point conductances
+  cond_curve site / sitebond realisations over trials and a grid of ps or
+             (ps, pb): the mean ConductCalc.m conductance curve (no reference
+             program; the batch kernel's ensemble, Context.batch_cond)
 
 Every compute step runs in libperc on the GPU; there is no fallback.
 """
@@ -97,6 +100,22 @@ def batch_supported(lattice, m, n, pbc=0):
     """perc_batch_supported (host-only): True when the batch kernel can run
     this lattice -- n >= 3, (n-2)*m <= 8192 interior rows, stencil operator."""
     return bool(L.lib().perc_batch_supported(lattice, m, n, pbc))
+
+
+def batch_cond_supported(kind, lattice, m, n, pbc=0):
+    """perc_batch_cond_supported (host-only): True when the batch kernel can
+    run this kind (BOND / SITE / SITEBOND) on this lattice -- batch_supported
+    for BOND, the same checks with the kind's own LDS layout for the others."""
+    return bool(L.lib().perc_batch_cond_supported(int(kind), lattice, m, n, pbc))
+
+
+KIND_RULE = {L.BOND: L.RULE_BOND, L.SITE: L.RULE_SITE, L.SITEBOND: L.RULE_MIXED}
+
+
+def natural_cur_rule(kind):
+    """the reference's own pairing: bondc.f's currents for the bond kind,
+    ConductCalc.m's for the site and mixed kinds"""
+    return L.CUR_FORTRAN if kind == L.BOND else L.CUR_MATLAB
 
 
 def scan_supported(lattice, m, n, pbc=0):
@@ -359,6 +378,51 @@ class Context:
         L.check(L.lib().perc_batch_bondc(self.h, o.shape[0], o.reshape(-1), len(it), it, ic,
                                          1 if solve else 0, Va, g0, leak, itol, tol, itmax,
                                          C.cast(out, C.c_void_p)), "perc_batch_bondc")
+        return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
+
+    def batch_cond(self, kind, item_trial, site_orders=None, bond_orders=None, item_nsites=None,
+                   item_nbonds=None, rule=None, cur_rule=None, solve=True, Va=1.0, g0=1.0, leak=LEAK,
+                   itol=2, tol=1e-8, itmax=2500):
+        """perc_batch_cond: many small bond, site or mixed realisations in one
+        launch, one workgroup each.  kind BOND: bond_orders (ntrials, nb + 1)
+        and item_nbonds; SITE: site_orders (ntrials, t + 1) and item_nsites;
+        SITEBOND: both.  Item i occupies the first item_nsites[i] sites and
+        item_nbonds[i] bonds of trial item_trial[i]'s orders.  rule=None: the
+        kind's rule (the only one the kernel runs); cur_rule=None: the
+        reference's own pairing (CUR_FORTRAN for BOND, CUR_MATLAB for SITE and
+        SITEBOND).  Returns one dict per item with batch_bondc's keys;
+        solve=False stops after the spanning test.  The dot order is the
+        context's."""
+        kind = int(kind)
+        if rule is None:
+            rule = KIND_RULE.get(kind, -1)  # (an unknown kind: libperc reports it)
+        if cur_rule is None:
+            cur_rule = natural_cur_rule(kind)
+        it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
+        so = bo = ns = nbc = None
+        ntrials = None
+        if site_orders is not None:
+            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
+            ntrials = so.shape[0]
+        if bond_orders is not None:
+            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
+            if ntrials is not None and bo.shape[0] != ntrials:
+                raise ValueError("site_orders and bond_orders differ in trials")
+            ntrials = bo.shape[0]
+        if ntrials is None:
+            ntrials = int(it.max()) + 1 if len(it) else 0  # (no list at all: libperc reports it)
+        if item_nsites is not None:
+            ns = np.ascontiguousarray(item_nsites, dtype=np.int32).reshape(-1)
+        if item_nbonds is not None:
+            nbc = np.ascontiguousarray(item_nbonds, dtype=np.int32).reshape(-1)
+        for c in (ns, nbc):
+            if c is not None and c.shape != it.shape:
+                raise ValueError("item_trial and the count lists differ in length")
+        out = (L.BatchItem * max(len(it), 1))()
+        L.check(L.lib().perc_batch_cond(self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so),
+                                        L.ptr(bo), len(it), L.ptr(it), L.ptr(ns), L.ptr(nbc),
+                                        1 if solve else 0, Va, g0, leak, itol, tol, itmax,
+                                        C.cast(out, C.c_void_p)), "perc_batch_cond")
         return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
 
     def batch_scan(self, kind, site_orders=None, bond_orders=None, scan=L.BOND, fixed=None):
@@ -785,6 +849,98 @@ def bond_cond_grid(lattice=0, m=10, n=10, pbc=0, master=58302, numtrials=1, Va=1
                 tr["perccln"] = ctx.label_numbers(L.BOND)["perccln"] if bfc else 0
             out.append(tr)
         return out
+    finally:
+        if own:
+            ctx.close()
+
+
+def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0.9, 1.0), master=58302,
+               numtrials=1, batch=256, cur_rule=None, Va=1.0, g0=1.0, tol=1e-8, itmax=2500, ctx=None,
+               device=0):
+    """The mean conductance curve of site or mixed percolation over trials:
+    G(ps) (kind SITE, site.f + ConductCalc.m's site rule; grid a list of ps) or
+    G(ps, pb) (kind SITEBOND, sitebond.f + the mixed rule; grid a list of
+    (ps, pb)).  Trial ii draws its orders once -- shuffled_ids(t, tseed(ii))
+    with trial_seeds(master) for SITE; shuffled_ids(t, sseed(ii)) and
+    shuffled_ids(nb, bseed(ii)) with paired_seeds(master), the alternate draw
+    of sb_perc.f / mixed_scan, for SITEBOND -- and every grid point occupies
+    the first int(ps * t) sites and int(pb * nb) bonds of them (site.f /
+    sitebond.f's truncation).  batch > 0 on a lattice batch_cond_supported
+    accepts: the (trial, point) items of about `batch` at a time (whole
+    trials) through Context.batch_cond; batch=0, or another lattice: each item
+    through occupy / label / conductance.  cur_rule=None: CUR_MATLAB, the
+    reference's pairing.  The dot order is the context's (ctx).  Returns
+    (trials, stats): per trial dict(ii, seed | sseed, bseed, rows) with one row
+    per grid point (ps, [pb,] nsites, [nbonds,] gbot, gtop, iter, spanning),
+    and the (npts, 5) statistics {count, sum Gtop, sum Gtop^2, count spanning,
+    sum iter} accumulated by perc_stats_accumulate in ascending (trial, point)
+    order -- the same sums in the same order either way, in the shape
+    Ensemble.bond_cond returns."""
+    if kind not in (L.SITE, L.SITEBOND):
+        raise ValueError("cond_curve: kind SITE or SITEBOND (bond: Ensemble.bond_cond)")
+    if numtrials < 0:
+        raise ValueError("numtrials < 0")
+    mixed = kind == L.SITEBOND
+    rule = KIND_RULE[kind]
+    if cur_rule is None:
+        cur_rule = natural_cur_rule(kind)
+    own = ctx is None
+    ctx = ctx or Context(lattice, m, n, pbc, device)
+    try:
+        t, nb = ctx.t, ctx.nb
+        pts = [(float(p[0]), float(p[1])) if mixed else (float(p), None) for p in grid]
+        npts = len(pts)
+        cnt_s = np.array([int(ps * t) for ps, _ in pts], np.int32)
+        cnt_b = np.array([int(pb * nb) for _, pb in pts], np.int32) if mixed else None
+        if mixed:
+            ss, bs = paired_seeds(master, max(numtrials, 1))
+        else:
+            ss, bs = trial_seeds(master, max(numtrials, 1)), None
+        batched = batch > 0 and npts > 0 and batch_cond_supported(kind, ctx.lattice, ctx.m, ctx.n, ctx.pbc)
+        group = max(1, batch // max(npts, 1)) if batched else 1
+        stats = np.zeros(npts * 5)
+        acc = L.lib().perc_stats_accumulate
+        out = []
+        for i0 in range(0, numtrials, group):
+            tr = range(i0, min(i0 + group, numtrials))
+            so = np.stack([shuffled_ids(t, int(ss[ii])) for ii in tr])
+            bo = np.stack([shuffled_ids(nb, int(bs[ii])) for ii in tr]) if mixed else None
+            if batched:
+                it = np.repeat(np.arange(len(tr), dtype=np.int32), npts)
+                res = ctx.batch_cond(kind, it, site_orders=so, bond_orders=bo,
+                                     item_nsites=np.tile(cnt_s, len(tr)),
+                                     item_nbonds=np.tile(cnt_b, len(tr)) if mixed else None,
+                                     cur_rule=cur_rule, Va=Va, g0=g0, leak=LEAK, itol=2, tol=tol,
+                                     itmax=itmax)
+            else:
+                res = []
+                for k in range(len(tr)):
+                    for j in range(npts):
+                        if mixed:
+                            ctx.occupy(kind, site_order=so[k], nsites=int(cnt_s[j]), bond_order=bo[k],
+                                       nbonds_=int(cnt_b[j]))
+                        else:
+                            ctx.occupy(kind, site_order=so[k], nsites=int(cnt_s[j]))
+                        li = ctx.label()
+                        c = ctx.conductance(rule, cur_rule, Va, g0, LEAK, 2, tol, itmax)
+                        res.append(dict(gtop=c["gtop"], gbot=c["gbot"], iter=c["iter"], nspan=li["nspan"]))
+            for k, ii in enumerate(tr):
+                rows = []
+                for j, (ps, pb) in enumerate(pts):
+                    r = res[k * npts + j]
+                    row = dict(ps=ps, nsites=int(cnt_s[j]))
+                    if mixed:
+                        row.update(pb=pb, nbonds=int(cnt_b[j]))
+                    row.update(gbot=r["gbot"], gtop=r["gtop"], iter=r["iter"], spanning=r["nspan"] > 0)
+                    rows.append(row)
+                    acc(stats, j, r["gtop"], int(r["nspan"] > 0), int(r["iter"]))
+                trial = dict(ii=ii + 1, rows=rows)
+                if mixed:
+                    trial.update(sseed=int(ss[ii]), bseed=int(bs[ii]))
+                else:
+                    trial.update(seed=int(ss[ii]))
+                out.append(trial)
+        return out, stats.reshape(npts, 5)
     finally:
         if own:
             ctx.close()

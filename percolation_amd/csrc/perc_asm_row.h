@@ -1,6 +1,6 @@
 // perc_asm_row.h -- one row of the Kirchhoff assembly (bondc.f:482-538,
 // ConductCalc.m:88-165): device code shared by perc_assemble.hip (k_assemble)
-// and perc_batch.hip (k_batch_bondc).  Anonymous namespace: each translation
+// and perc_batch.hip (k_batch_cond).  Anonymous namespace: each translation
 // unit keeps its own copy.
 #pragma once
 #include "perc_stencil.h"

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_csr_to_ell(int N, const int* __restr
 }
 
 // the closed-form rows' forms of the square lattice (k_assemble,
-// k_batch_bondc): interior, column-0 and column-(m-1) rows, -1 where the
+// k_batch_cond): interior, column-0 and column-(m-1) rows, -1 where the
 // general path runs; also the column classes of the nibble codes
 void asm_closed_forms(perc_ctx* h, int* fast_out, int* fl_out, int* fr_out) {
   // the square lattice's interior-column form (k_assemble's closed-form path)

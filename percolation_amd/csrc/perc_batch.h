@@ -1,7 +1,7 @@
-// perc_batch.h -- the batch path of libperc: many independent small bond
-// realisations in one launch, one workgroup per (trial, bond count) item
-// (perc_batch.hip: k_batch_bondc; perc_batch_host.cpp: the C-ABI and the
-// ensemble's batched trial loop).
+// perc_batch.h -- the batch path of libperc: many independent small
+// realisations (bond, site or mixed) in one launch, one workgroup per
+// (trial, counts) item (perc_batch.hip: k_batch_cond; perc_batch_host.cpp:
+// the C-ABI and the ensemble's batched trial loop).
 #pragma once
 #include "perc_internal.h"
 
@@ -25,11 +25,14 @@ struct BatchOut {
 // arrays -- parent (int, t + 1), the bond occupancy (nb + 1 bytes), the
 // member and spanning flags -- alias them: they are dead once the row codes,
 // the top row's rhs and the electrode rows' current codes are formed, before
-// the first iteration writes p.  The row codes follow whichever ends later.
+// the first iteration writes p.  The site and mixed kinds add one byte per
+// site (socc, t + 1 bytes) to the labeling view, after the spanning flags;
+// the bond kind's layout has none (oSocc = 0, unused).  The row codes follow
+// whichever view ends later.
 struct BatchLds {
-  int oQ, oBocc, oMem, oFlag, oC, oRed, oOff, oF, oRhs, oCur, oInt, total;
+  int oQ, oBocc, oMem, oFlag, oSocc, oC, oRed, oOff, oF, oRhs, oCur, oInt, total;
 };
-BatchLds batch_lds(const Geom& g);
+BatchLds batch_lds(const Geom& g, int kind = PERC_BOND);
 constexpr int kBatchLdsStatic = 2048;  // fold_chunk's term rows (static __shared__)
 constexpr int kBatchLdsMax = 160 * 1024;
 
@@ -38,17 +41,24 @@ constexpr int kBatchLdsMax = 160 * 1024;
 // it still fits: the geometry A/B of tools/cond_workers.py)
 int batch_threads(int N);
 
-// host-only checks of perc_batch_supported
-bool batch_supported(const Geom& g);
+// host-only checks of perc_batch_supported / perc_batch_cond_supported (the
+// kind's own LDS layout)
+bool batch_supported(const Geom& g, int kind = PERC_BOND);
 
 // device side (perc_batch.hip).  The orders' inverse permutations, once per
 // group of trials: rank[tr * nb + id - 1] = position of bond id in trial
 // tr's order (INT_MAX: not in it); then any number of launches over items of
-// those trials.  out[nitems]; iout[nitems * 2m] (solve != 0 only).
+// those trials.  out[nitems]; iout[nitems * 2m] (solve != 0 only).  The
+// site ranks (rank_s[tr * t + s - 1]) go beside them for the site and mixed
+// kinds; dev_batch_run reads the arrays its kind needs (item_nsites /
+// item_count may be NULL where the kind does not read them) and refuses an
+// item whose trial lies outside them.
 hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank);
-hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const int* item_count,
-                         int solve, double Va, double g0, double leak, int itol, double tol,
-                         int itmax, bool literal, BatchOut* out, double* iout);
+hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s);
+hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
+                         const int* item_nsites, const int* item_count, int solve, double Va,
+                         double g0, double leak, int itol, double tol, int itmax, bool literal,
+                         BatchOut* out, double* iout);
 void dev_batch_free(perc_ctx* h);
 // host side (perc_batch_host.cpp): perc_batch_bondc's two halves, so the
 // ensemble uploads a group's orders once and launches over them many times.
@@ -59,6 +69,16 @@ int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders);
 int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
                     const int* item_count, int solve, bool replay, double Va, double g0, double leak,
                     int itol, double tol, int itmax, perc_batch_item* out);
+// the same for any kind (batch_run_items is its bond kind under
+// PERC_CUR_FORTRAN): site_orders / item_nsites and bond_orders / item_nbonds
+// as perc_batch_cond takes them, the orders uploaded by batch_upload_orders /
+// batch_upload_site_orders
+int batch_upload_site_orders(perc_ctx* h, int ntrials, const int* site_orders);
+int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_orders,
+                         const int* bond_orders, int nitems, const int* item_trial,
+                         const int* item_nsites, const int* item_nbonds, int solve, bool replay,
+                         double Va, double g0, double leak, int itol, double tol, int itmax,
+                         perc_batch_item* out);
 // ---- threshold scans (perc_batch_scan.hip: k_batch_scan) ----------------
 // sites of the largest lattice one workgroup scans (128 x 128)
 constexpr int kScanSites = 16384;

@@ -1,7 +1,8 @@
-// perc_batch.hip -- k_batch_bondc: one workgroup takes one small bond
-// realisation (PERC_BOND, PERC_RULE_BOND, PERC_CUR_FORTRAN) from occupancy to
+// perc_batch.hip -- k_batch_cond: one workgroup takes one small realisation
+// (PERC_BOND with PERC_RULE_BOND, PERC_SITE with PERC_RULE_SITE or
+// PERC_SITEBOND with PERC_RULE_MIXED; either current rule) from occupancy to
 // terminal currents with no host round trip -- occupancy from the trial's
-// rank array, union-find labeling in LDS, the spanning rule of k_span_top,
+// rank arrays, union-find labeling in LDS, the spanning rule of k_span_top,
 // assemble_row, k_cg_small's loop (both dot orders) and k_currents' per-site
 // expression.  Many items per launch: the ensemble's (trial, grid point)
 // pairs side by side instead of a dozen launches and one busy CU each.
@@ -19,14 +20,16 @@ struct BatchArgs {
   int N, nb;
   const int* bond_first;
   const StencilForms* forms;
-  const int* rank;  // ntrials x nb
+  const int* rank;    // ntrials x nb (bond and mixed kinds)
+  const int* rank_s;  // ntrials x t (site and mixed kinds)
   const int* item_trial;
-  const int* item_count;
+  const int* item_count;   // occupied entries of the bond order (bond and mixed kinds)
+  const int* item_nsites;  // ... of the site order (site and mixed kinds)
   BatchOut* out;
   double* iout;  // nitems x 2m
   int* sflag;
   int fast, fl, fr, bf_closed;
-  int solve, itol, itmax;
+  int solve, itol, itmax, cur_rule;
   double Va, g0, leak, tol;
   BatchLds L;
 };
@@ -34,9 +37,14 @@ struct BatchArgs {
 // NT threads, rows t, t + NT, .. (at most kBatchEPT) per thread.  LIT: the
 // literal dot order (wave 0 folds every sum in ascending j, fold_chunk) --
 // bitwise k_fold_init + k_cg_small<true, true>; else per thread in row
-// order, wave butterfly, waves in order.
-template <int NT, bool LIT>
-__global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
+// order, wave butterfly, waves in order.  KIND: PERC_BOND / PERC_SITE /
+// PERC_SITEBOND, with the kind's own conductance rule (the rules' numbers are
+// the kinds').
+template <int NT, bool LIT, int KIND>
+__global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
+  static_assert(PERC_RULE_BOND == PERC_BOND && PERC_RULE_SITE == PERC_SITE &&
+                    PERC_RULE_MIXED == PERC_SITEBOND, "a kind's rule has its number");
+  constexpr int RULE = KIND;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Geom g = a.g;
   const int m = g.m, T = g.t, N = a.N;
@@ -47,6 +55,7 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
   uint8_t* bocc = reinterpret_cast<uint8_t*>(smem + a.L.oBocc);
   uint8_t* member = reinterpret_cast<uint8_t*>(smem + a.L.oMem);
   uint8_t* flag = reinterpret_cast<uint8_t*>(smem + a.L.oFlag);
+  uint8_t* socc = KIND != PERC_BOND ? reinterpret_cast<uint8_t*>(smem + a.L.oSocc) : nullptr;
   // solver view
   double* s_p = reinterpret_cast<double*>(smem);
   double* s_q = reinterpret_cast<double*>(smem + a.L.oQ);
@@ -58,11 +67,16 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
   uint16_t* s_cur = reinterpret_cast<uint16_t*>(smem + a.L.oCur);
   int* s_i = reinterpret_cast<int*>(smem + a.L.oInt);
 
-  const int count = a.item_count[item];
-  const int* __restrict__ rank = a.rank + (size_t)a.item_trial[item] * a.nb;
+  const int trial = a.item_trial[item];
+  const int count = KIND != PERC_SITE ? a.item_count[item] : 0;
+  const int nsite = KIND != PERC_BOND ? a.item_nsites[item] : 0;
+  const int* __restrict__ rank = KIND != PERC_SITE ? a.rank + (size_t)trial * a.nb : nullptr;
+  const int* __restrict__ rank_s = KIND != PERC_BOND ? a.rank_s + (size_t)trial * T : nullptr;
   BatchOut* out = a.out + item;
 
-  // ---- occupancy: bond id is occupied iff its position in the order < count
+  // ---- occupancy: an element is occupied iff its position in its order <
+  // its count.  Site kinds: the member flag is the occupied site (perc_cc.h);
+  // the site kind reads no bond ranks, bocc is all zero as perc_label leaves it
   {
     const int nw = (int)(sizeof(StencilForms) / 4);
     const int* src = reinterpret_cast<const int*>(a.forms);
@@ -72,21 +86,38 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
   if (t < 8) s_i[t] = t == 2 ? INT_MAX : 0;
   for (int s = t; s <= T; s += NT) {
     parent[s] = s;
-    member[s] = 0;
+    if constexpr (KIND == PERC_BOND) {
+      member[s] = 0;
+    } else {
+      const uint8_t o = s >= 1 && rank_s[s - 1] < nsite ? 1 : 0;
+      socc[s] = o;
+      member[s] = o;
+    }
   }
   for (int c = t; c <= m; c += NT) flag[c] = 0;
-  for (int id = t; id < a.nb; id += NT) bocc[id] = rank[id] < count ? 1 : 0;
+  if constexpr (KIND == PERC_SITE) {
+    for (int id = t; id < a.nb; id += NT) bocc[id] = 0;
+  } else {
+    for (int id = t; id < a.nb; id += NT) bocc[id] = rank[id] < count ? 1 : 0;
+  }
   load_forms(*a.forms, s_off);  // (ends with a workgroup barrier)
 
-  // ---- labeling: hook the larger root under the smaller over every occupied
-  // bond, flatten, until a pass hooks nothing (lds_label)
+  // ---- labeling: hook the larger root under the smaller over every bond
+  // that connects (cc_link's rule of the kind), flatten, until a pass hooks
+  // nothing (lds_label)
   lds_label<NT>(g, a.bond_first, parent, [&](int pass, int s, int, int q, int id) {
-    if (!bocc[id]) return false;
-    if (pass == 0) {
-      member[s] = 1;
-      member[q] = 1;
+    if constexpr (KIND == PERC_BOND) {
+      if (!bocc[id]) return false;
+      if (pass == 0) {
+        member[s] = 1;
+        member[q] = 1;
+      }
+      return true;
+    } else if constexpr (KIND == PERC_SITE) {
+      return socc[s] && socc[q];
+    } else {
+      return bocc[id] && socc[s] && socc[q];
     }
-    return true;
   });
 
   // ---- spanning (k_span_top's rule): root <= m and a top-row member
@@ -142,9 +173,9 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
   for (int i = t; i < N; i += NT) {
     uint16_t c;
     double b;
-    assemble_row_vals<false>(g, i, a.bond_first, bocc, nullptr, parent, nullptr, nullptr, nullptr, &b,
-                             &c, a.sflag, *sF, a.fast, a.fl, a.fr, a.bf_closed, PERC_RULE_BOND, g0,
-                             leak, Va, root, nullptr);
+    assemble_row_vals<false>(g, i, a.bond_first, bocc, socc, parent, nullptr, nullptr, nullptr, &b,
+                             &c, a.sflag, *sF, a.fast, a.fl, a.fr, a.bf_closed, RULE, g0, leak, Va,
+                             root, nullptr);
     s_c[i] = c;
     if (i >= N - m) s_rhs[i - (N - m)] = b;
   }
@@ -160,9 +191,7 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
       const int id = s < c ? bond_id(g, a.bond_first, s, c) : bond_id(g, a.bond_first, c, s);
       unsigned kind = 0;  // no bond: 0.0 (k_currents)
       if (id >= 0)
-        kind = bond_value(PERC_RULE_BOND, id, s, c, ps, bocc, nullptr, root, g0, leak, nullptr) == -g0
-                   ? 2u
-                   : 1u;
+        kind = bond_value(RULE, id, s, c, ps, bocc, socc, root, g0, leak, nullptr) == -g0 ? 2u : 1u;
       cc |= kind << (2 * j);
     }
     s_cur[idx] = (uint16_t)cc;
@@ -171,6 +200,10 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
 
   // ---- solve: k_cg_small<true, LIT>, the prologue included (x = 0, r = b)
   const double ng0 = -g0, nleak = -leak;
+  // the literal order at 1024 threads (128 VGPRs per thread) rebuilds a row's
+  // diagonal from its code in LDS where the p update needs it, rather than
+  // hold eight of them across the loop: the same value, and no scratch
+  constexpr bool kKeepDiag = !(LIT && NT == 1024);
   double rv[kBatchEPT], dv[kBatchEPT], xv[kBatchEPT];
 #pragma unroll
   for (int j = 0; j < kBatchEPT; ++j) {
@@ -252,7 +285,7 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
     for (int j = 0; j < kBatchEPT; ++j) {
       const int i = t + j * NT;
       if (i < N) {
-        const double z = rv[j] / dv[j];
+        const double z = rv[j] / (kKeepDiag ? dv[j] : code_diag(s_c[i], ng0, nleak));
         s_p[i] = k == 1 ? z : bk * s_p[i] + z;
       }
     }
@@ -346,8 +379,8 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
     if (!(err > tol) || k >= itmax + 1) break;
   }
 
-  // ---- currents: k_currents' PERC_CUR_FORTRAN expression on the 2m electrode
-  // sites, x through LDS (q is dead)
+  // ---- currents: k_currents' expression of the current rule on the 2m
+  // electrode sites, x through LDS (q is dead)
 #pragma unroll
   for (int j = 0; j < kBatchEPT; ++j) {
     const int i = t + j * NT;
@@ -371,9 +404,23 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
     }
     const double d = -rowsum;
     auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : x[c - m - 1]); };
-    double acc = d * V(s);
-    for (int j = 0; j < cnt; ++j)
-      if (fabs(gv[j]) >= 1.0e-10) acc = acc + gv[j] * V(nbr[j]);
+    double acc;
+    if (a.cur_rule == PERC_CUR_FORTRAN) {
+      acc = d * V(s);
+      for (int j = 0; j < cnt; ++j)
+        if (fabs(gv[j]) >= 1.0e-10) acc = acc + gv[j] * V(nbr[j]);
+    } else {  // no threshold, the diagonal term before the first neighbour > s
+      acc = 0.0;
+      bool done = false;
+      for (int j = 0; j < cnt; ++j) {
+        if (!done && nbr[j] > s) {
+          acc = acc + d * V(s);
+          done = true;
+        }
+        acc = acc + gv[j] * V(nbr[j]);
+      }
+      if (!done) acc = acc + d * V(s);
+    }
     iout[idx] = acc;
   }
   if (t == 0) {
@@ -384,26 +431,55 @@ __global__ __launch_bounds__(NT) void k_batch_bondc(BatchArgs a) {
 }
 
 struct BatchState {
-  int* d_rank = nullptr;
+  int* d_rank = nullptr;  // bond ranks, ntrials x nb
   size_t rank_cap = 0;
   int ntrials = 0;
-  int* d_items = nullptr;  // item_trial, then item_count
+  int* d_rank_s = nullptr;  // site ranks, ntrials_s x t
+  size_t rank_s_cap = 0;
+  int ntrials_s = 0;
+  int* d_items = nullptr;  // item_trial, then item_count, then item_nsites
   BatchOut* d_out = nullptr;
   double* d_iout = nullptr;
   size_t item_cap = 0, iout_cap = 0;
   int* d_sflag = nullptr;
-  int lds_attr[3][2] = {};  // dynamic LDS granted per instantiation
+  int lds_attr[3][2][3] = {};  // dynamic LDS granted per instantiation
 };
 
-template <int NT, bool LIT>
+template <int NT, bool LIT, int KIND>
 hipError_t launch(BatchState* B, int slot, const BatchArgs& a, int nitems, hipStream_t st) {
-  if (B->lds_attr[slot][LIT] < a.L.total) {  // dynamic LDS beyond the default limit
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_bondc<NT, LIT>),
+  if (B->lds_attr[slot][LIT][KIND] < a.L.total) {  // dynamic LDS beyond the default limit
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_cond<NT, LIT, KIND>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
-    B->lds_attr[slot][LIT] = a.L.total;
+    B->lds_attr[slot][LIT][KIND] = a.L.total;
   }
-  k_batch_bondc<NT, LIT><<<nitems, NT, a.L.total, st>>>(a);
-  return dbg_sync(st, "k_batch_bondc");
+  k_batch_cond<NT, LIT, KIND><<<nitems, NT, a.L.total, st>>>(a);
+  return dbg_sync(st, "k_batch_cond");
+}
+
+template <int NT>
+hipError_t launch_kind(BatchState* B, int slot, int kind, bool literal, const BatchArgs& a, int nitems,
+                       hipStream_t st) {
+  if (kind == PERC_BOND)
+    return literal ? launch<NT, true, PERC_BOND>(B, slot, a, nitems, st)
+                   : launch<NT, false, PERC_BOND>(B, slot, a, nitems, st);
+  if (kind == PERC_SITE)
+    return literal ? launch<NT, true, PERC_SITE>(B, slot, a, nitems, st)
+                   : launch<NT, false, PERC_SITE>(B, slot, a, nitems, st);
+  return literal ? launch<NT, true, PERC_SITEBOND>(B, slot, a, nitems, st)
+                 : launch<NT, false, PERC_SITEBOND>(B, slot, a, nitems, st);
+}
+
+// a rank array of n ints in *p (capacity *cap), copied from the host
+hipError_t upload_ranks(int** p, size_t* cap, size_t n, const int* rank, hipStream_t st) {
+  if (*cap < n) {
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    HIP_TRY(dmalloc(p, n));
+    *cap = n;
+  }
+  if (n) HIP_TRY(hipMemcpyAsync(*p, rank, sizeof(int) * n, hipMemcpyHostToDevice, st));
+  return hipStreamSynchronize(st);  // (the caller's array may go away)
 }
 
 }  // namespace
@@ -417,6 +493,7 @@ void dev_batch_free(perc_ctx* h) {
   BatchState* B = static_cast<BatchState*>(h->batch);
   if (!B) return;
   (void)hipFree(B->d_rank);
+  (void)hipFree(B->d_rank_s);
   (void)hipFree(B->d_items);
   (void)hipFree(B->d_out);
   (void)hipFree(B->d_iout);
@@ -433,37 +510,49 @@ const int* dev_batch_ranks(perc_ctx* h, int* ntrials) {
 
 hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank) {
   BatchState* B = batch_state(h);
-  const size_t n = (size_t)ntrials * (size_t)h->nb;
-  if (B->rank_cap < n) {
-    if (B->d_rank) HIP_TRY(hipFree(B->d_rank));
-    B->d_rank = nullptr;
-    B->rank_cap = 0;
-    HIP_TRY(dmalloc(&B->d_rank, n));
-    B->rank_cap = n;
-  }
+  B->ntrials = 0;
+  HIP_TRY(upload_ranks(&B->d_rank, &B->rank_cap, (size_t)ntrials * (size_t)h->nb, rank, h->stream));
   B->ntrials = ntrials;
-  if (!B->d_sflag) {
-    HIP_TRY(dmalloc(&B->d_sflag, 4));
-    HIP_TRY(hipMemsetAsync(B->d_sflag, 0, 4 * sizeof(int), h->stream));
-  }
-  if (n) HIP_TRY(hipMemcpyAsync(B->d_rank, rank, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-  return hipStreamSynchronize(h->stream);  // (the caller's array may go away)
+  return hipSuccess;
 }
 
-hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const int* item_count,
-                         int solve, double Va, double g0, double leak, int itol, double tol,
-                         int itmax, bool literal, BatchOut* out, double* iout) {
+hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s) {
+  BatchState* B = batch_state(h);
+  B->ntrials_s = 0;
+  HIP_TRY(upload_ranks(&B->d_rank_s, &B->rank_s_cap, (size_t)ntrials * (size_t)h->g.t, rank_s, h->stream));
+  B->ntrials_s = ntrials;
+  return hipSuccess;
+}
+
+hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
+                         const int* item_nsites, const int* item_count, int solve, double Va,
+                         double g0, double leak, int itol, double tol, int itmax, bool literal,
+                         BatchOut* out, double* iout) {
   if (nitems == 0) return hipSuccess;
   BatchState* B = batch_state(h);
   hipStream_t st = h->stream;
   const int m = h->g.m;
+  const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
+  // every item's trial must lie in the uploaded rank arrays the kind reads
+  int have = INT_MAX;
+  if (need_b) have = std::min(have, B->d_rank ? B->ntrials : 0);
+  if (need_s) have = std::min(have, B->d_rank_s ? B->ntrials_s : 0);
+  for (int i = 0; i < nitems; ++i)
+    if (item_trial[i] < 0 || item_trial[i] >= have) {
+      set_error("k_batch_cond: an item's trial lies outside the uploaded rank arrays");
+      return hipErrorInvalidValue;
+    }
+  if (!B->d_sflag) {
+    HIP_TRY(dmalloc(&B->d_sflag, 4));
+    HIP_TRY(hipMemsetAsync(B->d_sflag, 0, 4 * sizeof(int), st));
+  }
   if (B->item_cap < (size_t)nitems) {
     if (B->d_items) HIP_TRY(hipFree(B->d_items));
     if (B->d_out) HIP_TRY(hipFree(B->d_out));
     B->d_items = nullptr;
     B->d_out = nullptr;
     B->item_cap = 0;
-    HIP_TRY(dmalloc(&B->d_items, 2 * (size_t)nitems));
+    HIP_TRY(dmalloc(&B->d_items, 3 * (size_t)nitems));
     HIP_TRY(dmalloc(&B->d_out, (size_t)nitems));
     B->item_cap = nitems;
   }
@@ -476,7 +565,11 @@ hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const i
     B->iout_cap = niout;
   }
   HIP_TRY(hipMemcpyAsync(B->d_items, item_trial, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(B->d_items + nitems, item_count, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
+  if (need_b)
+    HIP_TRY(hipMemcpyAsync(B->d_items + nitems, item_count, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
+  if (need_s)
+    HIP_TRY(hipMemcpyAsync(B->d_items + 2 * (size_t)nitems, item_nsites, sizeof(int) * nitems,
+                           hipMemcpyHostToDevice, st));
   // an item that stops before the currents leaves its iout row unwritten
   if (niout) HIP_TRY(hipMemsetAsync(B->d_iout, 0, sizeof(double) * niout, st));
   BatchArgs a;
@@ -486,8 +579,10 @@ hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const i
   a.bond_first = h->d.bond_first;
   a.forms = h->d.forms_dev;
   a.rank = B->d_rank;
+  a.rank_s = B->d_rank_s;
   a.item_trial = B->d_items;
   a.item_count = B->d_items + nitems;
+  a.item_nsites = B->d_items + 2 * (size_t)nitems;
   a.out = B->d_out;
   a.iout = B->d_iout;
   a.sflag = B->d_sflag;
@@ -496,16 +591,17 @@ hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const i
   a.solve = solve;
   a.itol = itol;
   a.itmax = itmax;
+  a.cur_rule = cur_rule;
   a.Va = Va;
   a.g0 = g0;
   a.leak = leak;
   a.tol = tol;
-  a.L = batch_lds(h->g);
+  a.L = batch_lds(h->g, kind);
   const int nt = batch_threads(h->N);
   hipError_t e;
-  if (nt == 256) e = literal ? launch<256, true>(B, 0, a, nitems, st) : launch<256, false>(B, 0, a, nitems, st);
-  else if (nt == 512) e = literal ? launch<512, true>(B, 1, a, nitems, st) : launch<512, false>(B, 1, a, nitems, st);
-  else e = literal ? launch<1024, true>(B, 2, a, nitems, st) : launch<1024, false>(B, 2, a, nitems, st);
+  if (nt == 256) e = launch_kind<256>(B, 0, kind, literal, a, nitems, st);
+  else if (nt == 512) e = launch_kind<512>(B, 1, kind, literal, a, nitems, st);
+  else e = launch_kind<1024>(B, 2, kind, literal, a, nitems, st);
   HIP_TRY(e);
   int flag = 0;
   HIP_TRY(hipMemcpyAsync(out, B->d_out, sizeof(BatchOut) * nitems, hipMemcpyDeviceToHost, st));
@@ -513,10 +609,11 @@ hipError_t dev_batch_run(perc_ctx* h, int nitems, const int* item_trial, const i
   HIP_TRY(hipMemcpyAsync(&flag, B->d_sflag, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (flag & 3) {  // a row without its stencil bond or form: perc_batch_supported excludes it
-    set_error("k_batch_bondc: a row does not fit the stencil operator");
+    set_error("k_batch_cond: a row does not fit the stencil operator");
     return hipErrorInvalidValue;
   }
   return hipSuccess;
 }
 
 }  // namespace perc
+

@@ -1,6 +1,6 @@
 // perc_batch_host.cpp -- host side of the batch path (include/perc.h:
-// perc_batch_supported, perc_batch_bondc, perc_scan_supported,
-// perc_batch_scan): argument checks, the orders' inverse permutations, the
+// perc_batch_supported, perc_batch_bondc, perc_batch_cond_supported,
+// perc_batch_cond, perc_scan_supported, perc_batch_scan): argument checks, the orders' inverse permutations, the
 // launch geometry and LDS layouts, the fold of the terminal currents and the
 // single-path replay of the items several clusters span.
 #include <hip/hip_runtime.h>
@@ -17,7 +17,7 @@
 
 namespace perc {
 
-BatchLds batch_lds(const Geom& g) {
+BatchLds batch_lds(const Geom& g, int kind) {
   auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
   const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
   BatchLds L{};
@@ -26,7 +26,11 @@ BatchLds batch_lds(const Geom& g) {
   L.oBocc = up16(4 * ((long long)g.t + 1));
   L.oMem = L.oBocc + up16(nb + 1);
   L.oFlag = L.oMem + up16(g.t + 1);
-  const int label_end = L.oFlag + up16(g.m + 1);
+  int label_end = L.oFlag + up16(g.m + 1);
+  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
+    L.oSocc = label_end;
+    label_end = L.oSocc + up16((long long)g.t + 1);
+  }
   L.oC = std::max(solver_end, label_end);
   L.oRed = L.oC + up16(2 * N);
   L.oOff = L.oRed + up16(48 * sizeof(double));
@@ -47,7 +51,7 @@ int batch_threads(int N) {
   return nt;
 }
 
-bool batch_supported(const Geom& g) {
+bool batch_supported(const Geom& g, int kind) {
   if (g.n < 3 || g.m < 3) return false;
   if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
   const long long N = (long long)(g.n - 2) * g.m;
@@ -75,7 +79,7 @@ bool batch_supported(const Geom& g) {
       if (!bond) return false;
     }
   }
-  const BatchLds L = batch_lds(g);
+  const BatchLds L = batch_lds(g, kind);
   return L.total + kBatchLdsStatic <= kBatchLdsMax;
 }
 
@@ -121,10 +125,41 @@ int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders) {
   return PERC_OK;
 }
 
-int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
-                    const int* item_count, int solve, bool replay, double Va, double g0, double leak,
-                    int itol, double tol, int itmax, perc_batch_item* out) {
-  const int nb = (int)h->nb, m = h->g.m;
+int batch_upload_site_orders(perc_ctx* h, int ntrials, const int* site_orders) {
+  const int t = h->g.t;
+  hipSetDevice(h->device);
+  std::vector<int> rank((size_t)ntrials * t);
+  order_ranks(ntrials, t, site_orders, rank.data());
+  hipError_t e = dev_batch_upload_sites(h, ntrials, rank.data());
+  if (e != hipSuccess) return hip_status(e, "perc_batch_cond/upload");
+  return PERC_OK;
+}
+
+// the first cnt entries of an order of N + 1 as perc_occupy takes them: the
+// whole order (cnt > N) with the spill slot dropped
+static bool occupy_prefix(const int* o, int cnt, int N, std::vector<int>* list, const int** src,
+                          int* len) {
+  *src = o;
+  *len = cnt;
+  if (cnt <= N) return true;
+  list->clear();
+  for (int k = 0; k < cnt; ++k)
+    if (o[k] != 0) list->push_back(o[k]);
+  if ((int)list->size() > N) return false;
+  *src = list->data();
+  *len = (int)list->size();
+  return true;
+}
+
+int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_orders,
+                         const int* bond_orders, int nitems, const int* item_trial,
+                         const int* item_nsites, const int* item_nbonds, int solve, bool replay,
+                         double Va, double g0, double leak, int itol, double tol, int itmax,
+                         perc_batch_item* out) {
+  const int nb = (int)h->nb, m = h->g.m, t = h->g.t;
+  const int rule = kind;  // (PERC_RULE_* of a kind has the kind's number)
+  const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
+  const char* who = kind == PERC_BOND && cur_rule == PERC_CUR_FORTRAN ? "perc_batch_bondc" : "perc_batch_cond";
   hipSetDevice(h->device);
   hipError_t e;
   const bool literal = h->dot_order != PERC_DOT_FAST;
@@ -132,12 +167,13 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
   const int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
   std::vector<BatchOut> bo((size_t)std::min(nitems, chunk));
   std::vector<double> iout(solve ? bo.size() * 2 * (size_t)m : 0);
-  std::vector<int> list;
+  std::vector<int> slist, blist;
   for (int i0 = 0; i0 < nitems; i0 += chunk) {
     const int n = std::min(chunk, nitems - i0);
-    e = dev_batch_run(h, n, item_trial + i0, item_count + i0, solve ? 1 : 0, Va, g0, leak, itol, tol,
-                      itmax, literal, bo.data(), iout.data());
-    if (e != hipSuccess) return hip_status(e, "perc_batch_bondc");
+    e = dev_batch_run(h, kind, cur_rule, n, item_trial + i0, need_s ? item_nsites + i0 : nullptr,
+                      need_b ? item_nbonds + i0 : nullptr, solve ? 1 : 0, Va, g0, leak, itol, tol, itmax,
+                      literal, bo.data(), iout.data());
+    if (e != hipSuccess) return hip_status(e, who);
     for (int i = 0; i < n; ++i) {
       perc_batch_item& it = out[i0 + i];
       const BatchOut& b = bo[i];
@@ -153,20 +189,17 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
       if (b.fallback && replay) {
         // several clusters span: the reference's lowest-label rule through
         // the single path, on the context
-        const int* o = orders + (size_t)item_trial[i0 + i] * (nb + 1);
-        const int cnt = item_count[i0 + i];
-        const int* src = o;
-        int len = cnt;
-        if (cnt > nb) {  // the whole order: the spill slot dropped
-          list.clear();
-          for (int k = 0; k < cnt; ++k)
-            if (o[k] != 0) list.push_back(o[k]);
-          if ((int)list.size() > nb) return PERC_EINVAL;
-          src = list.data();
-          len = (int)list.size();
-        }
+        const int tr = item_trial[i0 + i];
+        const int *ssrc = nullptr, *bsrc = nullptr;
+        int slen = 0, blen = 0;
+        if (need_s && !occupy_prefix(site_orders + (size_t)tr * (t + 1), item_nsites[i0 + i], t, &slist,
+                                     &ssrc, &slen))
+          return PERC_EINVAL;
+        if (need_b && !occupy_prefix(bond_orders + (size_t)tr * (nb + 1), item_nbonds[i0 + i], nb, &blist,
+                                     &bsrc, &blen))
+          return PERC_EINVAL;
         perc_label_info li{};
-        int rc = perc_occupy(h, PERC_BOND, 0, nullptr, len, src);
+        int rc = perc_occupy(h, kind, slen, ssrc, blen, bsrc);
         if (!rc) rc = perc_label(h, &li, nullptr);
         if (rc) return rc;
         it.nclusters = li.nclusters;
@@ -175,8 +208,7 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
         it.span_sites = li.span_sites;
         if (solve) {
           perc_cond_result res{};
-          rc = perc_conductance(h, PERC_RULE_BOND, PERC_CUR_FORTRAN, Va, g0, leak, itol, tol, itmax,
-                                &res, nullptr);
+          rc = perc_conductance(h, rule, cur_rule, Va, g0, leak, itol, tol, itmax, &res, nullptr);
           if (rc) return rc;
           it.gtop = res.gtop;
           it.gbot = res.gbot;
@@ -185,12 +217,20 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
           it.status = res.status;
         }
       } else if (solve && b.status == 0) {
-        // currents_impl's ascending fold (bondc.f:587-590)
+        // currents_impl's folds: ascending (bondc.f:587-590), or Itop from
+        // site t downward (ConductCalc.m:191-194)
         const double* io = iout.data() + (size_t)i * 2 * m;
         double Ibot = 0.0, Itop = 0.0;
-        for (int c = 0; c < m; ++c) {
-          Ibot = Ibot + io[c];
-          Itop = Itop + io[m + c];
+        if (cur_rule == PERC_CUR_FORTRAN) {
+          for (int c = 0; c < m; ++c) {
+            Ibot = Ibot + io[c];
+            Itop = Itop + io[m + c];
+          }
+        } else {
+          for (int c = 0; c < m; ++c) {
+            Ibot = io[c] + Ibot;
+            Itop = io[2 * m - 1 - c] + Itop;
+          }
         }
         it.gtop = Itop / Va;
         it.gbot = std::fabs(Ibot) / Va;
@@ -198,6 +238,13 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
     }
   }
   return PERC_OK;
+}
+
+int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
+                    const int* item_count, int solve, bool replay, double Va, double g0, double leak,
+                    int itol, double tol, int itmax, perc_batch_item* out) {
+  return batch_run_items_kind(h, PERC_BOND, PERC_CUR_FORTRAN, nullptr, orders, nitems, item_trial, nullptr,
+                              item_count, solve, replay, Va, g0, leak, itol, tol, itmax, out);
 }
 
 int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out) {
@@ -249,6 +296,54 @@ int perc_batch_bondc(perc_ctx* h, int ntrials, const int* orders, int nitems, co
   if (rc) return rc;
   return batch_run_items(h, orders, nitems, item_trial, item_count, solve, true, Va, g0, leak, itol,
                          tol, itmax, out);
+}
+
+int perc_batch_cond_supported(int kind, int lattice, int m, int n, int pbc) {
+  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND) return 0;
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n >= (1LL << 31) - 16) return 0;
+  return batch_supported(make_geom(lattice, m, n, pbc), kind) ? 1 : 0;
+}
+
+int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, const int* site_orders,
+                    const int* bond_orders, int nitems, const int* item_trial, const int* item_nsites,
+                    const int* item_nbonds, int solve, double Va, double g0, double leak, int itol,
+                    double tol, int itmax, perc_batch_item* out) {
+  if (!h) return PERC_EINVAL;
+  auto bad = [](const char* text) {
+    set_error(std::string("perc_batch_cond: ") + text);
+    return PERC_EINVAL;
+  };
+  const bool pair = (kind == PERC_BOND && rule == PERC_RULE_BOND) ||
+                    (kind == PERC_SITE && rule == PERC_RULE_SITE) ||
+                    (kind == PERC_SITEBOND && rule == PERC_RULE_MIXED);
+  if (!pair)
+    return bad("kind / rule PERC_BOND / PERC_RULE_BOND, PERC_SITE / PERC_RULE_SITE or PERC_SITEBOND / "
+               "PERC_RULE_MIXED only");
+  if (cur_rule != PERC_CUR_FORTRAN && cur_rule != PERC_CUR_MATLAB)
+    return bad("cur_rule PERC_CUR_FORTRAN or PERC_CUR_MATLAB only");
+  if (ntrials < 0 || nitems < 0) return bad("ntrials or nitems < 0");
+  if (itmax < 0) return bad("itmax < 0");
+  if (solve && itol != 1 && itol != 2) return bad("itol 1 or 2 only");
+  if (!batch_supported(h->g, kind))
+    return bad("lattice not supported by the batch kernel for this kind (perc_batch_cond_supported)");
+  const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
+  if (ntrials && ((need_s && !site_orders) || (need_b && !bond_orders)))
+    return bad("an order list the kind reads is missing");
+  if (nitems && (!item_trial || !out || (need_s && !item_nsites) || (need_b && !item_nbonds)))
+    return bad("item_trial, out or a count list the kind reads is missing");
+  const int t = h->g.t, nb = (int)h->nb;
+  for (int i = 0; i < nitems; ++i) {
+    if (item_trial[i] < 0 || item_trial[i] >= ntrials) return bad("item_trial outside 0..ntrials-1");
+    if (need_s && (item_nsites[i] < 0 || item_nsites[i] > t + 1)) return bad("item_nsites outside 0..t+1");
+    if (need_b && (item_nbonds[i] < 0 || item_nbonds[i] > nb + 1)) return bad("item_nbonds outside 0..nb+1");
+  }
+  if (nitems == 0) return PERC_OK;
+  int rc = need_b ? batch_upload_orders(h, ntrials, bond_orders) : PERC_OK;
+  if (!rc && need_s) rc = batch_upload_site_orders(h, ntrials, site_orders);
+  if (rc) return rc;
+  return batch_run_items_kind(h, kind, cur_rule, site_orders, bond_orders, nitems, item_trial, item_nsites,
+                              item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out);
 }
 
 int perc_scan_supported(int lattice, int m, int n, int pbc) {

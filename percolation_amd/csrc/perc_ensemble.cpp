@@ -191,7 +191,7 @@ int perc_ensemble_set_workers(perc_ensemble* e, int workers) {
 int perc_ensemble_workers(perc_ensemble* e) { return e ? e->workers : PERC_EINVAL; }
 
 // Batch path of perc_ensemble_bond_cond: about `items` (trial, grid point)
-// realisations per launch of k_batch_bondc, one workgroup each (0, the
+// realisations per launch of k_batch_cond, one workgroup each (0, the
 // default: the per-trial loop).  Ignored on a lattice perc_batch_supported
 // refuses: perc_ensemble_batch then returns 0.
 int perc_ensemble_set_batch(perc_ensemble* e, int items) {

@@ -2,7 +2,7 @@
 """bond_cond trials per second on one GPU through perc_ensemble_bond_cond
 with W workers (contexts, host threads, streams) per device, and with the
 batch path (perc_ensemble_set_batch: about B (trial, grid point) items per
-launch of k_batch_bondc, one workgroup each; one worker).
+launch of k_batch_cond, one workgroup each; one worker).
 
   python tools/cond_workers.py [--L 64,128 --trials 16 --workers 1,2,4,8,16
                                 --batch 0,64,256,1024 --repeats 3]

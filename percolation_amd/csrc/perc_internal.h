@@ -43,6 +43,11 @@ struct StencilForms {
   unsigned umask;  // union of rmask over the regular forms
 };
 constexpr unsigned kRmapIrregular = 0xEEEEEEEEu;
+// rmask of the square lattice's interior form: raster positions 1, 3, 4, 6
+// ((-1,0) (0,-1) (0,1) (1,0)).  The nibble-code march kernels build their
+// stencil from it at compile time, so the host gives them nibble codes only
+// where the interior form is regular with exactly this mask
+constexpr unsigned kSqRasterMask = 0x5Au;
 
 // Device-resident CG scalars (one cache line each group; written only by the
 // last-arriving workgroup of a kernel, read by the next kernel).

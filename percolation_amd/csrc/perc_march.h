@@ -500,7 +500,11 @@ __device__ __forceinline__ double mwin_at(int kp, const MWin& U, const MWin& C, 
 
 // q of element E: d x + sum over the form's slots (slot order) of g x_nb,
 // when the wave's rows all share one regular form (slot order = raster
-// order) with used-position bits `mask` (wave-uniform: scalar branches)
+// order) with used-position bits `mask`.  `mask` is wave-uniform but a
+// run-time value: the compiler emits no branches for it -- it evaluates all
+// 8 positions (bit test, two selects for gv, multiply, add, two selects that
+// keep or drop the sum) and carries the slot counter j in registers.  The
+// u16-code kernels (any lattice) take this form.
 template <int E>
 __device__ __forceinline__ double march_q(unsigned c, double d, double xi, unsigned mask,
                                           const MWin& U, const MWin& C, const MWin& D,
@@ -516,6 +520,30 @@ __device__ __forceinline__ double march_q(unsigned c, double d, double xi, unsig
     }
   }
   return acc;
+}
+
+// the same sum with the position mask known at compile time: only the
+// form's own positions are evaluated, slot indices are constants.  Bitwise
+// march_q's value for mask == MASK: the same terms in the same slot order
+// with the same operands (a position march_q skips keeps acc by a select,
+// it is not added as zero).  The nibble-code kernels (open square lattice,
+// MASK = kSqRasterMask) take this form.
+template <int E, unsigned MASK, int KP = 0, int J = 0>
+__device__ __forceinline__ double march_q_from(double acc, unsigned c, const MWin& U, const MWin& C,
+                                               const MWin& D, double ng0, double nleak) {
+  if constexpr (KP == 8) {
+    return acc;
+  } else if constexpr ((MASK >> KP) & 1u) {
+    const double gv = ((c >> J) & 1u) ? ng0 : nleak;
+    return march_q_from<E, MASK, KP + 1, J + 1>(acc + gv * mwin_at<E>(KP, U, C, D), c, U, C, D, ng0, nleak);
+  } else {
+    return march_q_from<E, MASK, KP + 1, J>(acc, c, U, C, D, ng0, nleak);
+  }
+}
+template <int E, unsigned MASK>
+__device__ __forceinline__ double march_q(unsigned c, double d, double xi, const MWin& U,
+                                          const MWin& C, const MWin& D, double ng0, double nleak) {
+  return march_q_from<E, MASK>(d * xi, c, U, C, D, ng0, nleak);
 }
 
 // general path (rows whose wave mixes forms, or wrapped-column forms): the
@@ -820,7 +848,14 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
     // (the row-major nibble march runs on the open square lattice only --
     // the host takes the u16 codes with pbc -- so the other paths are not
     // compiled into it: their registers spilled it at the 4-wave bound)
+    // (PERC_MARCH_PIN_SQ: for counting the open-square walk's instructions
+    // only, tools/march_isa.py -- such a build is wrong under pbc and is
+    // never loaded)
+#if defined(PERC_MARCH_PIN_SQ)
+    if constexpr (PK) sqp = true;
+#else
     if constexpr (PK && !SM) sqp = true;
+#endif
     else if constexpr (PK) sqp = !a.T.pbc;
     else if constexpr (SM || kMarchRmSq) sqp = a.sqcls && !__any((((c0w ^ g.cb0) | (c1w ^ g.cb1)) >> 8) != 0u);
     else sqp = false;
@@ -838,7 +873,22 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
       // edge form sent the whole edge-strip wave to march_q_map: edge
       // strips walked 69.8 vs 65.9 us (P, iteration 20000) and set the
       // kernel's end (profiles/r5_2_mtrace_summary_it20000_L4096.txt)
-      const unsigned mask = a.St.F.rmask[a.ncls[0] >> 11];
+      //
+      // Nibble codes (PK): the interior form's mask is kSqRasterMask, checked
+      // by the host before it hands out nibble codes (sq_nibble_form), so
+      // the four terms are built at compile time.  With the run-time mask P
+      // issued 234 VALU instructions per step (85 of them v_cndmask) and 105
+      // SALU, with an s_load of rmask and its lgkmcnt(0) wait; with the
+      // constant 153 (37) and 57 (tools/march_isa.py,
+      // profiles/cmask_march_isa_*): P 69.3 vs 75.2 us, B 71.8 vs 75.2 us, the
+      // solve 0.1403 vs 0.1495 ms per iteration, bitwise the same
+      // (profiles/cmask_ab_L4096.json).
+      // PERC_MARCH_DYNMASK (A/B probe builds only) restores the run-time mask.
+#if defined(PERC_MARCH_DYNMASK)
+      constexpr bool cmask = false;
+#else
+      constexpr bool cmask = PK;
+#endif
       unsigned e0, e1;
       if constexpr (SM) {
         e0 = (c0w & g.lo0) | ((c0w & g.hi0) << 1);
@@ -847,8 +897,14 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
         e0 = g.col == 0 ? (c0w & 1u) | ((c0w & 6u) << 1) : c0w & 0xFu;
         e1 = g.col + 1 == a.T.m - 1 ? (c1w & 3u) | ((c1w & 4u) << 1) : c1w & 0xFu;
       }
-      q0 = march_q<0>(e0, dM0.x, W.C.e0, mask, W.U, W.C, W.Dn, ng0, nleak);
-      q1 = march_q<1>(e1, dM1.x, W.C.e1, mask, W.U, W.C, W.Dn, ng0, nleak);
+      if constexpr (cmask) {
+        q0 = march_q<0, kSqRasterMask>(e0, dM0.x, W.C.e0, W.U, W.C, W.Dn, ng0, nleak);
+        q1 = march_q<1, kSqRasterMask>(e1, dM1.x, W.C.e1, W.U, W.C, W.Dn, ng0, nleak);
+      } else {
+        const unsigned mask = a.St.F.rmask[a.ncls[0] >> 11];
+        q0 = march_q<0>(e0, dM0.x, W.C.e0, mask, W.U, W.C, W.Dn, ng0, nleak);
+        q1 = march_q<1>(e1, dM1.x, W.C.e1, mask, W.U, W.C, W.Dn, ng0, nleak);
+      }
     } else if (uni) {
       const unsigned mask = a.St.F.rmask[ff];
       q0 = march_q<0>(c0w, dM0.x, W.C.e0, mask, W.U, W.C, W.Dn, ng0, nleak);
@@ -929,14 +985,16 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
   }
 }
 
-template <int MODE, int D, bool UP, bool SM, int PAUX = 0, bool PK = false, bool LIT = false, int ESR = 0>
-__device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, const MBuf& B,
-                                           MRow (&ring)[D],
-                                           bool first, double bk, double ak,
-                                           const double* __restrict__ psrc,
-                                           double* __restrict__ pnew, const double2* s_dt,
-                                           const unsigned* s_rpos, const unsigned* s_rmap,
-                                           double* s_w, double (&acc)[2], double2* s_ed = nullptr) {
+// FT >= 0: `first` is the compile-time constant FT != 0 (march_walk below)
+template <int MODE, int D, bool UP, bool SM, int PAUX, bool PK, bool LIT, int ESR, int FT>
+__device__ __forceinline__ void march_walk_f(const CGArgs& a, const MGeom& g, const MBuf& B,
+                                             MRow (&ring)[D],
+                                             bool first_rt, double bk, double ak,
+                                             const double* __restrict__ psrc,
+                                             double* __restrict__ pnew, const double2* s_dt,
+                                             const unsigned* s_rpos, const unsigned* s_rmap,
+                                             double* s_w, double (&acc)[2], double2* s_ed) {
+  const bool first = FT < 0 ? first_rt : FT != 0;
   MState W;
   W.U = MWin{0.0, 0.0, 0.0, 0.0};
   W.C = W.U;
@@ -956,6 +1014,41 @@ __device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, cons
       march_step<MODE, UP, SM, LIT, PK, ESR>(a, g, B, R, UP ? g.rend - j : g.r0 - 1 + j, first, bk, ak, pnew, s_dt,
                                             s_rpos, s_rmap, s_w, W, acc, s_ed);
     }
+  }
+}
+
+// The walk of one band.  Nibble-code P kernels: the first iteration's walk
+// (k == 1, one launch per solve: p(0) = z, no p(k-1) loads) and every other
+// iteration's are two instantiations chosen by one wave-uniform branch here,
+// so the steps carry no `first` selects (on p's two elements, the halo p and
+// the p(k-1) load offsets): strip-major P 146 instead of 153 VALU
+// instructions per step, the solve 0.1390 vs 0.1403 ms per iteration in
+// every one of 5 rounds (profiles/cmask_ab_L4096.json: `first` vs `main`).
+// PERC_MARCH_FIRST_RT (A/B probe builds only): the run-time `first` in
+// every step, as the u16 kernels keep it.
+template <int MODE, int D, bool UP, bool SM, int PAUX = 0, bool PK = false, bool LIT = false, int ESR = 0>
+__device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, const MBuf& B,
+                                           MRow (&ring)[D],
+                                           bool first, double bk, double ak,
+                                           const double* __restrict__ psrc,
+                                           double* __restrict__ pnew, const double2* s_dt,
+                                           const unsigned* s_rpos, const unsigned* s_rmap,
+                                           double* s_w, double (&acc)[2], double2* s_ed = nullptr) {
+#if defined(PERC_MARCH_FIRST_RT)
+  constexpr bool split = false;
+#else
+  constexpr bool split = MODE != kMarchB && PK;
+#endif
+  if constexpr (split) {
+    if (first)
+      march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, 1>(a, g, B, ring, true, bk, ak, psrc, pnew, s_dt, s_rpos, s_rmap,
+                                                           s_w, acc, s_ed);
+    else
+      march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, 0>(a, g, B, ring, false, bk, ak, psrc, pnew, s_dt, s_rpos, s_rmap,
+                                                           s_w, acc, s_ed);
+  } else {
+    march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, -1>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos, s_rmap,
+                                                          s_w, acc, s_ed);
   }
 }
 

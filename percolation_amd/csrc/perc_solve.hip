@@ -177,6 +177,15 @@ void launch_spmv(perc_ctx* h, const CGArgs& a, const double* x, double* y) {
   else k_spmv_st<6><<<h->grid, kBlock, 0, h->stream>>>(a.St, x, y);
 }
 
+// The nibble-code march kernels build the interior form's four terms from
+// kSqRasterMask at compile time (march_step): nibble codes only where that
+// form (bits 11.. of the interior column class) is regular with exactly this
+// mask; any other lattice keeps the u16 codes and their run-time mask.
+bool sq_nibble_form(const perc_ctx* h) {
+  const int f = h->ncls[0] >> 11;
+  return f >= 0 && f < h->forms.nforms && h->forms.regular[f] && h->forms.rmask[f] == kSqRasterMask;
+}
+
 // the row-major march's nibble codes (vectors past the Infinity Cache, the
 // open square lattice, PERC_MARCH_NIBBLE): 0.5 instead of 2 bytes of row
 // code per element in P and B (24.5 + 48m / N instead of 26 B per row; B
@@ -188,8 +197,8 @@ hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
   hipStream_t st = h->stream;
   h->nib_used = false;
   a.rm_pnib = h->knobs.rm_pu16 ? 0 : 1;
-  if (!kMarchRmNib || !h->nib_ok || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) || !h->march || !h->qfree ||
-      a.sm)
+  if (!kMarchRmNib || !h->nib_ok || !sq_nibble_form(h) || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) ||
+      !h->march || !h->qfree || a.sm)
     return hipSuccess;
   const long long n = (long long)a.T.nrows * a.T.m;
   if (!d.nib_sm) HIP_TRY(dmalloc(&d.nib_sm, (size_t)h->N / 2 + 16));
@@ -565,7 +574,7 @@ hipError_t to_strips(perc_ctx* h, CGArgs& a) {
   // nibble codes (PERC_MARCH_NIBBLE, square lattice): 0.5 instead of 2
   // bytes of row code per element in both march kernels
   h->nib_used = false;
-  if (h->nib_ok && (h->march_mode & PERC_MARCH_NIBBLE)) {
+  if (h->nib_ok && sq_nibble_form(h) && (h->march_mode & PERC_MARCH_NIBBLE)) {
     if (!d.nib_sm) HIP_TRY(dmalloc(&d.nib_sm, (size_t)h->N / 2 + 16));
     HIP_TRY(hipMemsetAsync(d.sflag + 3, 0, sizeof(int), st));
     k_pack_nib<true><<<blocks_for(n / 2), kBlock, 0, st>>>(a.T, d.code, d.nib_sm, h->ncls[0], h->ncls[1],

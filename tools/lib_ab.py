@@ -121,6 +121,7 @@ def main():
         libs.append((name, "main", spec))
     best = {}
     fps = {}
+    per_round = {}  # every round's figures: a gain counts only if every round shows it
     for _ in range(args.rounds):
         for name, lib, spec in libs:
             env = dict(os.environ)
@@ -136,10 +137,12 @@ def main():
                 raise SystemExit("child %s failed rc=%d" % (name, r.returncode))
             o = json.loads(r.stdout.strip().splitlines()[-1])
             fps.setdefault(name, o.pop("fp"))
+            per_round.setdefault(name, []).append({k: round(v, 5) for k, v in o.items()})
             b = best.setdefault(name, {})
             for k, v in o.items():
                 b[k] = min(b.get(k, 9e9), v)
     out = {lib: {k: round(v, 5) for k, v in b.items()} for lib, b in best.items()}
+    out["rounds"] = per_round
     out["fingerprints"] = fps
     out["L"] = args.L
     print(json.dumps(out), flush=True)

@@ -792,7 +792,10 @@ void perc_shuffle_seeded(int seed, int N, int *order);
  * matrix from COMMON /mat/ sa(NMAX), ija(NMAX) (symbol mat_, NMAX=20000 as
  * in the reference) unless perc_nr_bind() points them at other storage.
  * linbcg_ runs the HIP PCG on device 0.  Errors that `pause` in the
- * reference are reported through perc_nr_status(). */
+ * reference are reported through perc_nr_status().  Malformed storage is
+ * PERC_EMISMATCH before any device call: ija(1) != n+2, a column outside
+ * 1..n, descending row pointers, and on the bound paths ija(n+1)-1 > nmax
+ * (perc_nr_bind's nmax; nmax <= 0 there means NMAX). */
 void sprsin_(double *a, int *n, int *np, double *thresh, int *nmax, double *sa, int *ija);
 void dsprsax_(double *sa, int *ija, double *x, double *b, int *n);
 void dsprstx_(double *sa, int *ija, double *x, double *b, int *n);

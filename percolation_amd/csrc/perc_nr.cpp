@@ -54,35 +54,63 @@ extern BlankCommon __BLNK__ __attribute__((weak));
 
 namespace {
 
-bool bound(double** sa, int** ija) {
+// the bound storage and its declared length: perc_nr_bind's nmax, or NMAX of
+// COMMON /mat/
+bool bound(double** sa, int** ija, int* nmax) {
   if (g_sa) {
     *sa = g_sa;
     *ija = g_ija;
+    *nmax = g_nmax;
     return true;
   }
   if (&mat_ != nullptr) {
     *sa = mat_.sa;
     *ija = mat_.ija;
+    *nmax = kNmaxDefault;
     return true;
   }
   return false;
 }
 
-// NR (1-based, in 0-based arrays) -> 0-based CSR of the off-diagonals
-int nr_to_csr(const double* sa, const int* ija, int n, std::vector<int>& rowptr,
+// NR (1-based, in 0-based arrays) -> 0-based CSR of the off-diagonals.
+// Malformed storage is PERC_EMISMATCH before anything is indexed by it:
+// ija(1) != n+2 (bondc.f:891), row pointers that descend, a column outside
+// 1..n, and, where the storage's length is known (nmax > 0: the bound
+// paths), ija(n+1)-1 > nmax.  dsprsax_ / dsprstx_ take bare arrays (nmax 0).
+int nr_to_csr(const double* sa, const int* ija, int n, int nmax, std::vector<int>& rowptr,
               std::vector<int>& col, std::vector<double>& val, std::vector<double>& diag) {
-  if (ija[0] != n + 2) return PERC_EMISMATCH;  // bondc.f:891
+  if (ija[0] != n + 2) {  // 'mismatched vector and matrix in dsprsax' (bondc.f:891)
+    set_error("NR storage: ija(1) is not n+2");
+    return PERC_EMISMATCH;
+  }
+  if (nmax > 0 && n + 1 > nmax) {
+    set_error("NR storage: ija(1..n+1) does not fit nmax");
+    return PERC_EMISMATCH;
+  }
   const int base = n + 2;
   rowptr.resize(n + 1);
-  for (int i = 0; i <= n; ++i) rowptr[i] = ija[i] - base;
+  rowptr[0] = 0;
+  for (int i = 1; i <= n; ++i) {
+    rowptr[i] = ija[i] - base;
+    if (rowptr[i] < rowptr[i - 1]) {
+      set_error("NR storage: row pointers ija(1..n+1) descend");
+      return PERC_EMISMATCH;
+    }
+  }
   const int nnz = rowptr[n];
-  if (nnz < 0) return PERC_EMISMATCH;
+  if (nmax > 0 && ija[n] - 1 > nmax) {
+    set_error("NR storage: ija(n+1)-1 exceeds nmax");
+    return PERC_EMISMATCH;
+  }
   col.resize(nnz);
   val.resize(nnz);
   for (int k = 0; k < nnz; ++k) {
     col[k] = ija[base - 1 + k] - 1;
     val[k] = sa[base - 1 + k];
-    if (col[k] < 0 || col[k] >= n) return PERC_EMISMATCH;
+    if (col[k] < 0 || col[k] >= n) {
+      set_error("NR storage: a column index outside 1..n");
+      return PERC_EMISMATCH;
+    }
   }
   diag.assign(sa, sa + n);
   return PERC_OK;
@@ -138,6 +166,12 @@ int upload(int n, const std::vector<int>& rowptr, const std::vector<int>& col,
     e = hipMemcpy(g_nr->d.val, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess)
     e = hipMemcpy(g_nr->d.diag, diag.data(), sizeof(double) * n, hipMemcpyHostToDevice);
+  // csr_row<NS> loads entry min(a + j, last) of every row unconditionally and
+  // gathers x at its column; for empty rows at the end of the matrix that
+  // entry is index nnz, in the 8-entry pad of dev_alloc_matrix: column 0,
+  // value 0 there (the product is not added: j < b - a is false)
+  if (e == hipSuccess) e = hipMemset(g_nr->d.col + col.size(), 0, sizeof(int) * 8);
+  if (e == hipSuccess) e = hipMemset(g_nr->d.val + val.size(), 0, sizeof(double) * 8);
   return hip_status(e, "nr upload");
 }
 
@@ -197,11 +231,11 @@ void sprsin_(double* a, int* n_, int* np_, double* thresh_, int* nmax_, double* 
   }
 }
 
-static void spmv_nr(double* sa, int* ija, double* x, double* b, int n, bool transpose) {
+static void spmv_nr(double* sa, int* ija, int nmax, double* x, double* b, int n, bool transpose) {
   std::lock_guard<std::mutex> lk(g_nr_mu);
   std::vector<int> rowptr, col;
   std::vector<double> val, diag;
-  g_status = nr_to_csr(sa, ija, n, rowptr, col, val, diag);
+  g_status = nr_to_csr(sa, ija, n, nmax, rowptr, col, val, diag);
   if (g_status) return;
   if (transpose && !is_symmetric(n, rowptr, col, val)) {
     // build the explicit transpose (host re-indexing only; product on device)
@@ -225,35 +259,40 @@ static void spmv_nr(double* sa, int* ija, double* x, double* b, int n, bool tran
   g_nr->assembled = true;
   g_status = hip_status(dev_spmv(g_nr, x, b), "dsprsax_");
 }
-static void spmv_nr_checked(double* sa, int* ija, double* x, double* b, int n, bool transpose) {
-  spmv_nr(sa, ija, x, b, n, transpose);
+static void spmv_nr_checked(double* sa, int* ija, int nmax, double* x, double* b, int n,
+                            bool transpose) {
+  spmv_nr(sa, ija, nmax, x, b, n, transpose);
   nr_report(transpose ? "dsprstx_" : "dsprsax_");
 }
 
 // b = A x (bondc.f:887-899)
 void dsprsax_(double* sa, int* ija, double* x, double* b, int* n) {
-  spmv_nr_checked(sa, ija, x, b, *n, false);
+  spmv_nr_checked(sa, ija, 0, x, b, *n, false);
 }
 // b = A' x (bondc.f:902-917)
 void dsprstx_(double* sa, int* ija, double* x, double* b, int* n) {
-  spmv_nr_checked(sa, ija, x, b, *n, true);
+  spmv_nr_checked(sa, ija, 0, x, b, *n, true);
 }
 
 void atimes_(int* n, double* x, double* r, int* itrnsp) {  // bondc.f:841-852
   double* sa;
   int* ija;
-  if (!bound(&sa, &ija)) {
+  int nmax;
+  if (!bound(&sa, &ija, &nmax)) {
+    set_error("no matrix bound: neither COMMON /mat/ nor perc_nr_bind");
     g_status = PERC_ESTATE;
     return;
   }
-  spmv_nr_checked(sa, ija, x, r, *n, *itrnsp != 0);
+  spmv_nr_checked(sa, ija, nmax, x, r, *n, *itrnsp != 0);
 }
 
 void asolve_(int* n, double* b, double* x, int* itrnsp) {  // bondc.f:855-864
   (void)itrnsp;
   double* sa;
   int* ija;
-  if (!bound(&sa, &ija)) {
+  int nmax;
+  if (!bound(&sa, &ija, &nmax)) {
+    set_error("no matrix bound: neither COMMON /mat/ nor perc_nr_bind");
     g_status = PERC_ESTATE;
     return;
   }
@@ -289,17 +328,20 @@ static void linbcg_impl(int* n_, double* b, double* x, int* itol, double* tol, i
   *iter = 0;
   double* sa;
   int* ija;
-  if (!bound(&sa, &ija)) {
+  int nmax;
+  if (!bound(&sa, &ija, &nmax)) {
+    set_error("no matrix bound: neither COMMON /mat/ nor perc_nr_bind");
     g_status = PERC_ESTATE;
     return;
   }
   if (*itol < 1 || *itol > 4) {  // 'illegal itol in linbcg'
+    set_error("linbcg_: illegal itol");
     g_status = PERC_EITOL;
     return;
   }
   std::vector<int> rowptr, col;
   std::vector<double> val, diag;
-  g_status = nr_to_csr(sa, ija, n, rowptr, col, val, diag);
+  g_status = nr_to_csr(sa, ija, n, nmax, rowptr, col, val, diag);
   if (g_status) return;
   if (!is_symmetric(n, rowptr, col, val)) {
     set_error("linbcg_: non-symmetric matrix; device path implements the symmetric case");

@@ -248,3 +248,38 @@ def bondc(lattice, m, n, pbc, pb, seed, Va=1.0, g0=1.0, itmax=2500, tol=1e-8,
     out = {k: getattr(res, k) for k, _ in BondcResult._fields_}
     out.update(label=label, csize=csize, o1=o1, o2=o2)
     return out
+
+
+# ------------------------------------------ NR storage (sa, ija) directly
+def nr_ax(sa, ija, x, transpose=False):
+    """or_dsprsax / or_dsprstx of a matrix given in NR storage"""
+    n = int(ija[0]) - 2
+    y = f64(n)
+    f = lib().or_dsprstx if transpose else lib().or_dsprsax
+    f(sa, ija, np.ascontiguousarray(x, dtype=np.float64), y, n)
+    return y
+
+
+def nr_linbcg(sa, ija, b, x0, itol, tol, itmax):
+    """or_linbcg (bondc.f:750-838, literal) from the start x0; returns
+    (x, iter, err)"""
+    n = int(ija[0]) - 2
+    x = np.array(x0, dtype=np.float64, copy=True)
+    it, err = C.c_int(), C.c_double()
+    lib().or_linbcg(sa, ija, n, np.ascontiguousarray(b, dtype=np.float64), x, itol, tol, itmax,
+                    C.byref(it), C.byref(err), None)
+    return x, it.value, err.value
+
+
+def nr_linbcg_sym(sa, ija, b, iters, dot_order):
+    """x after exactly `iters` iterations of or_linbcg_sym (itol 2, from x =
+    0, no tolerance stop) with its dot products in the given association"""
+    n = int(ija[0]) - 2
+    x = f64(n)
+    it, err = C.c_int(), C.c_double()
+    rc = lib().or_linbcg_sym(sa, ija, n, np.ascontiguousarray(b, dtype=np.float64), x, iters - 1, 1,
+                             0, f64(1), f64(1), i32(1), f64(1), C.byref(it), C.byref(err), None,
+                             dot_order)
+    assert rc == 0, "matrix not bitwise symmetric"
+    assert it.value == iters, (it.value, iters)
+    return x

@@ -718,6 +718,63 @@ int perc_batch_scan(perc_ctx *h, int kind, int scan, int ntrials,
                     const int *bond_orders /* ntrials x (nb+1) */,
                     const int *fixed, perc_scan_item *out);
 
+/* ---- occupation orders shuffled on the device (one wave per trial) ---- *
+ * The batch entry points above take whole orders from the host: one serial
+ * perc_shuffle_seeded per trial, the orders' inverse permutations, 4 bytes
+ * per element per trial uploaded.  perc_batch_shuffle runs the same shuffle
+ * -- srand(seed) on a stream local to the trial, then the REAL*4
+ * Fisher-Yates of bondc.f:162-174 with the spill slot (hazard H2), the
+ * generator's recurrence and the REAL*4 mapping operation for operation --
+ * for ntrials trials at once, one wave each, the order in LDS as N + 1
+ * entries of 16 bits, and leaves the inverse permutations in the context's
+ * batch rank buffers, where perc_batch_cond's and perc_batch_scan's kernels
+ * read them: rank[trial * N + id - 1] = position of id.  The orders are the
+ * host's bit for bit (seed 0 is 123459876; a negative seed wraps as unsigned
+ * 64 bit in the first update, as in perc_shuffle_seeded).
+ *   list PERC_BOND: N = nb, the bond ranks; PERC_SITE: N = t, the site ranks.
+ * orders_out (ntrials rows of N + 1, as perc_shuffle_seeded leaves them) and
+ * ranks_out (ntrials rows of N) may each be NULL.  perc_batch_scan_seeded
+ * and perc_batch_cond_seeded are perc_batch_scan and perc_batch_cond with
+ * seed lists (one seed per trial) in place of the order lists: the same
+ * argument rules, the same chunking, the same results item for item; an item
+ * of perc_batch_cond_seeded that falls back to the single path (fallback =
+ * 1) gets its trial's order(s) from perc_shuffle_seeded on the host.
+ * ntrials == 0 is PERC_OK.  PERC_EINVAL (text in perc_last_error), before
+ * any device call: a list perc_shuffle_device_supported refuses, a missing
+ * seed list that the kind reads, ntrials < 0, a bad list, kind or scan.
+ * One serial wave per trial loses to the host while few trials share a
+ * call: measured at 50 x 50, the seeded scan runs at 0.8-0.9
+ * of the order-taking one's rate at 1..8 trials per call, draws level at 16
+ * and wins from there (1.2 x at 32, 3-4 x at 256, 7-13 x at 1000).  Nothing
+ * takes this path unless asked. */
+/* host-only: 1 when the shuffle kernel can take a list of N ids: N >= 1,
+   N + 1 <= 65535 (ids and the target N + 1 in 16 bits) and the LDS arena --
+   2 (N + 1) bytes for the order, 256 for the swap targets of 64 steps --
+   within a workgroup's 160 KB.  Every list of a lattice perc_scan_supported
+   or perc_batch_cond_supported accepts passes (the longest: the 48896 bonds
+   of the triangular 128 x 128 pbc lattice). */
+int perc_shuffle_device_supported(int N);
+int perc_batch_shuffle(perc_ctx *h, int list, int ntrials, const int *seeds,
+                       int *orders_out /* ntrials x (N+1), or NULL */,
+                       int *ranks_out /* ntrials x N, or NULL */);
+/* the same kernel on a list of N ids that is no list of the context's
+   lattice (any N perc_shuffle_device_supported accepts): the outputs only,
+   the context's batch rank buffers stay as they are */
+int perc_batch_shuffle_n(perc_ctx *h, int N, int ntrials, const int *seeds,
+                         int *orders_out, int *ranks_out);
+int perc_batch_scan_seeded(perc_ctx *h, int kind, int scan, int ntrials,
+                           const int *site_seeds /* ntrials */,
+                           const int *bond_seeds /* ntrials */,
+                           const int *fixed, perc_scan_item *out);
+int perc_batch_cond_seeded(perc_ctx *h, int kind, int rule, int cur_rule, int ntrials,
+                           const int *site_seeds /* ntrials, NULL for PERC_BOND */,
+                           const int *bond_seeds /* ntrials, NULL for PERC_SITE */,
+                           int nitems, const int *item_trial,
+                           const int *item_nsites /* NULL for PERC_BOND */,
+                           const int *item_nbonds /* NULL for PERC_SITE */,
+                           int solve, double Va, double g0, double leak, int itol,
+                           double tol, int itmax, perc_batch_item *out);
+
 /* ---- ensemble statistics (bond_cond, config 4) ----------------------- */
 /* Accumulate stats for one pb point: {count, sum G, sum G^2, count spanning,
    sum iter} into acc[5*point..]. */

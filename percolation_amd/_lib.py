@@ -190,6 +190,13 @@ SIGNATURES = {
                                   C.c_double, C.c_int, _VP]),
     "perc_scan_supported": (C.c_int, [C.c_int] * 4),
     "perc_batch_scan": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
+    "perc_shuffle_device_supported": (C.c_int, [C.c_int]),
+    "perc_batch_shuffle": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP]),
+    "perc_batch_shuffle_n": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP]),
+    "perc_batch_scan_seeded": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
+    "perc_batch_cond_seeded": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP,
+                                         _VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                         C.c_double, C.c_int, _VP]),
     "perc_ensemble_ctx": (C.c_void_p, [_VP, C.c_int]),
     "perc_ensemble_trials": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP]),
     "perc_ensemble_allreduce": (C.c_int, [_VP, _D, C.c_int]),

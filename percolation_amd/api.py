@@ -124,6 +124,18 @@ def scan_supported(lattice, m, n, pbc=0):
     return bool(L.lib().perc_scan_supported(lattice, m, n, pbc))
 
 
+def shuffle_device_supported(N):
+    """perc_shuffle_device_supported (host-only): True when the shuffle kernel
+    can take a list of N ids -- 1 <= N <= 65534 (16-bit entries in LDS)."""
+    return bool(L.lib().perc_shuffle_device_supported(int(N)))
+
+
+def _device_shuffle_ok(ctx, kind):
+    """every list `kind` reads on ctx's lattice fits the shuffle kernel"""
+    return ((kind == L.BOND or shuffle_device_supported(ctx.t))
+            and (kind == L.SITE or shuffle_device_supported(ctx.nb)))
+
+
 class Context:
     """One libperc context (one lattice on one device)."""
 
@@ -380,9 +392,34 @@ class Context:
                                          C.cast(out, C.c_void_p)), "perc_batch_bondc")
         return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
 
+    def batch_shuffle(self, list, seeds, orders=False, ranks=False, n=None):
+        """perc_batch_shuffle: the reference shuffle of one trial per seed on
+        the device, one wave each, the ranks left in the context's batch rank
+        buffers.  list BOND (N = nb) or SITE (N = t).  Returns (orders, ranks):
+        the (ntrials, N + 1) orders as shuffled_ids gives them and the
+        (ntrials, N) positions of ids 1..N in them, each None unless asked
+        for.  n (list=None): perc_batch_shuffle_n, a list of n ids that is no
+        list of the lattice -- the outputs only, the rank buffers left alone."""
+        sd = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        if n is not None:
+            if list is not None:
+                raise ValueError("list or n, not both")
+            N = int(n)
+        else:
+            N = self.nb if int(list) == L.BOND else self.t
+        o = np.zeros((len(sd), max(N, 0) + 1), dtype=np.int32) if orders else None
+        r = np.zeros((len(sd), max(N, 0)), dtype=np.int32) if ranks else None
+        if n is not None:
+            L.check(L.lib().perc_batch_shuffle_n(self.h, N, len(sd), L.ptr(sd), L.ptr(o), L.ptr(r)),
+                    "perc_batch_shuffle_n")
+        else:
+            L.check(L.lib().perc_batch_shuffle(self.h, int(list), len(sd), L.ptr(sd), L.ptr(o), L.ptr(r)),
+                    "perc_batch_shuffle")
+        return o, r
+
     def batch_cond(self, kind, item_trial, site_orders=None, bond_orders=None, item_nsites=None,
                    item_nbonds=None, rule=None, cur_rule=None, solve=True, Va=1.0, g0=1.0, leak=LEAK,
-                   itol=2, tol=1e-8, itmax=2500):
+                   itol=2, tol=1e-8, itmax=2500, site_seeds=None, bond_seeds=None):
         """perc_batch_cond: many small bond, site or mixed realisations in one
         launch, one workgroup each.  kind BOND: bond_orders (ntrials, nb + 1)
         and item_nbonds; SITE: site_orders (ntrials, t + 1) and item_nsites;
@@ -392,7 +429,9 @@ class Context:
         reference's own pairing (CUR_FORTRAN for BOND, CUR_MATLAB for SITE and
         SITEBOND).  Returns one dict per item with batch_bondc's keys;
         solve=False stops after the spanning test.  The dot order is the
-        context's."""
+        context's.  site_seeds / bond_seeds (one seed per trial) in place of
+        the order lists: perc_batch_cond_seeded, the orders shuffled on the
+        device -- the same items."""
         kind = int(kind)
         if rule is None:
             rule = KIND_RULE.get(kind, -1)  # (an unknown kind: libperc reports it)
@@ -401,6 +440,18 @@ class Context:
         it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
         so = bo = ns = nbc = None
         ntrials = None
+        seeded = site_seeds is not None or bond_seeds is not None
+        if seeded:
+            if site_orders is not None or bond_orders is not None:
+                raise ValueError("orders or seeds, not both")
+            if site_seeds is not None:
+                so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
+                ntrials = len(so)
+            if bond_seeds is not None:
+                bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
+                if ntrials is not None and len(bo) != ntrials:
+                    raise ValueError("site_seeds and bond_seeds differ in trials")
+                ntrials = len(bo)
         if site_orders is not None:
             so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
             ntrials = so.shape[0]
@@ -419,10 +470,11 @@ class Context:
             if c is not None and c.shape != it.shape:
                 raise ValueError("item_trial and the count lists differ in length")
         out = (L.BatchItem * max(len(it), 1))()
-        L.check(L.lib().perc_batch_cond(self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so),
-                                        L.ptr(bo), len(it), L.ptr(it), L.ptr(ns), L.ptr(nbc),
-                                        1 if solve else 0, Va, g0, leak, itol, tol, itmax,
-                                        C.cast(out, C.c_void_p)), "perc_batch_cond")
+        name = "perc_batch_cond_seeded" if seeded else "perc_batch_cond"
+        L.check(getattr(L.lib(), name)(self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so),
+                                       L.ptr(bo), len(it), L.ptr(it), L.ptr(ns), L.ptr(nbc),
+                                       1 if solve else 0, Va, g0, leak, itol, tol, itmax,
+                                       C.cast(out, C.c_void_p)), name)
         return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
 
     def batch_scan(self, kind, site_orders=None, bond_orders=None, scan=L.BOND, fixed=None):
@@ -431,9 +483,27 @@ class Context:
         orders, (ntrials, N + 1) shuffled id arrays (one array for one
         trial); kind SITEBOND: both lists, scan names the scanned one and
         fixed (an int or one per trial) the occupied entries of the other.
-        Returns one dict per trial (first, maxcs, span_size, nspan)."""
+        Returns one dict per trial (first, maxcs, span_size, nspan).
+        batch_scan_seeded takes seeds in place of the order lists."""
+        return self._batch_scan(kind, site_orders, bond_orders, scan, fixed, None, None, False)
+
+    def batch_scan_seeded(self, kind, site_seeds=None, bond_seeds=None, scan=L.BOND, fixed=None):
+        """perc_batch_scan_seeded: batch_scan with site_seeds / bond_seeds
+        (one seed per trial) in place of the order lists, the orders shuffled
+        on the device (one wave per trial) -- the same records."""
+        return self._batch_scan(kind, None, None, scan, fixed, site_seeds, bond_seeds, True)
+
+    def _batch_scan(self, kind, site_orders, bond_orders, scan, fixed, site_seeds, bond_seeds, seeded):
         so = bo = fx = None
         ntrials = None
+        if site_seeds is not None:
+            so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
+            ntrials = len(so)
+        if bond_seeds is not None:
+            bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
+            if ntrials is not None and len(bo) != ntrials:
+                raise ValueError("site_seeds and bond_seeds differ in trials")
+            ntrials = len(bo)
         if site_orders is not None:
             so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
             ntrials = so.shape[0]
@@ -452,8 +522,9 @@ class Context:
         if ntrials is None:
             ntrials = 1  # (no list at all: libperc reports it)
         out = (L.ScanItem * max(ntrials, 1))()
-        L.check(L.lib().perc_batch_scan(self.h, int(kind), int(scan), ntrials, L.ptr(so), L.ptr(bo),
-                                        L.ptr(fx), C.cast(out, C.c_void_p)), "perc_batch_scan")
+        name = "perc_batch_scan_seeded" if seeded else "perc_batch_scan"
+        L.check(getattr(L.lib(), name)(self.h, int(kind), int(scan), ntrials, L.ptr(so), L.ptr(bo),
+                                       L.ptr(fx), C.cast(out, C.c_void_p)), name)
         return [{k: getattr(out[i], k) for k, _ in L.ScanItem._fields_} for i in range(ntrials)]
 
     def bondc_realisation(self, order, tbonds, Va=1.0, g0=1.0, tol=1e-8, itmax=2500,
@@ -644,7 +715,7 @@ def first_spanning(ctx, order, kind=L.BOND, n=None):
 
 
 def threshold_scan(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, master=58302, numtrials=10,
-                   ctx=None, device=0, replay=False, batch=0):
+                   ctx=None, device=0, replay=False, batch=0, device_shuffle=False):
     """bond_perc / site_perc (Fortran/Square/bond_perc.f, site_perc.f): per
     trial ii, seed tseed(ii) = int(rand(0)*1e6)+1, the reference shuffle,
     then the first occupation count that spans; the record is (tseed,
@@ -654,7 +725,9 @@ def threshold_scan(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, master=58302, numt
     gives the reference label number perccln).  batch > 0 (on a lattice
     scan_supported accepts, without replay): the orders of `batch` trials at
     a time shuffled on the host, one perc_batch_scan call per group -- the
-    same records."""
+    same records.  device_shuffle=True (with batch > 0, on such a lattice,
+    ignored otherwise): the group's orders shuffled on the device from the
+    seeds (perc_batch_scan_seeded), no shuffled_ids call -- the same records."""
     own = ctx is None
     ctx = ctx or Context(lattice, m, n, pbc, device)
     try:
@@ -664,8 +737,11 @@ def threshold_scan(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, master=58302, numt
         if batch > 0 and not replay and scan_supported(ctx.lattice, ctx.m, ctx.n, ctx.pbc):
             for i0 in range(0, numtrials, batch):
                 sd = seeds[i0:min(i0 + batch, numtrials)]
-                orders = np.stack([shuffled_ids(N, int(s)) for s in sd])
-                res = ctx.batch_scan(kind, **{"bond_orders" if kind == L.BOND else "site_orders": orders})
+                if device_shuffle and _device_shuffle_ok(ctx, kind):
+                    res = ctx.batch_scan_seeded(kind, **{"bond_seeds" if kind == L.BOND else "site_seeds": sd})
+                else:
+                    orders = np.stack([shuffled_ids(N, int(s)) for s in sd])
+                    res = ctx.batch_scan(kind, **{"bond_orders" if kind == L.BOND else "site_orders": orders})
                 for s, r in zip(sd, res):
                     c = r["first"] if r["first"] else N
                     out.append(dict(tseed=int(s), count=c,
@@ -729,7 +805,7 @@ def paired_seeds(pseed, k=1000):
 
 
 def mixed_scan(lattice=0, m=50, n=50, pbc=0, scan=L.BOND, master=8811064, points=None,
-               iters=100, as_built=True, ctx=None, device=0, batch=0):
+               iters=100, as_built=True, ctx=None, device=0, batch=0, device_shuffle=False):
     """sb_perc (scan=BOND: sites fixed at ps, bonds added until a mixed
     cluster spans; Square/sb_perc.f) / bs_perc (scan=SITE: bonds fixed at
     pb, sites added; Square/bs_perc.f).  points: the ps (sb) / pb (bs)
@@ -741,7 +817,9 @@ def mixed_scan(lattice=0, m=50, n=50, pbc=0, scan=L.BOND, master=8811064, points
     H11) or, with as_built=False, the GPU bisection of the intended rule.
     batch > 0 (on a lattice scan_supported accepts; not the as-built bs_perc,
     a host replay): the GPU bisections of `batch` trials at a time in one
-    perc_batch_scan call -- the same records."""
+    perc_batch_scan call -- the same records.  device_shuffle=True (with
+    batch > 0 taking effect, ignored otherwise): both orders of those trials
+    shuffled on the device from sseed / bseed (perc_batch_scan_seeded)."""
     own = ctx is None
     ctx = ctx or Context(lattice, m, n, pbc, device)
     try:
@@ -761,9 +839,13 @@ def mixed_scan(lattice=0, m=50, n=50, pbc=0, scan=L.BOND, master=8811064, points
                 fx = int(pt * t) if scan == L.BOND else int(pt * nb)  # sb_perc.f:210, bs_perc.f:209
                 for j0 in range(0, iters, batch):
                     jr = range(j0, min(j0 + batch, iters))
-                    so = np.stack([shuffled_ids(t, int(ss[jj])) for jj in jr])
-                    bo = np.stack([shuffled_ids(nb, int(bs[jj])) for jj in jr])
-                    res = ctx.batch_scan(L.SITEBOND, site_orders=so, bond_orders=bo, scan=scan, fixed=fx)
+                    if device_shuffle and _device_shuffle_ok(ctx, L.SITEBOND):
+                        res = ctx.batch_scan_seeded(L.SITEBOND, site_seeds=ss[jr.start:jr.stop],
+                                                    bond_seeds=bs[jr.start:jr.stop], scan=scan, fixed=fx)
+                    else:
+                        so = np.stack([shuffled_ids(t, int(ss[jj])) for jj in jr])
+                        bo = np.stack([shuffled_ids(nb, int(bs[jj])) for jj in jr])
+                        res = ctx.batch_scan(L.SITEBOND, site_orders=so, bond_orders=bo, scan=scan, fixed=fx)
                     for jj, r in zip(jr, res):
                         first = r["first"]
                         if scan == L.BOND:
@@ -856,7 +938,7 @@ def bond_cond_grid(lattice=0, m=10, n=10, pbc=0, master=58302, numtrials=1, Va=1
 
 def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0.9, 1.0), master=58302,
                numtrials=1, batch=256, cur_rule=None, Va=1.0, g0=1.0, tol=1e-8, itmax=2500, ctx=None,
-               device=0):
+               device=0, device_shuffle=False):
     """The mean conductance curve of site or mixed percolation over trials:
     G(ps) (kind SITE, site.f + ConductCalc.m's site rule; grid a list of ps) or
     G(ps, pb) (kind SITEBOND, sitebond.f + the mixed rule; grid a list of
@@ -868,7 +950,10 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
     sitebond.f's truncation).  batch > 0 on a lattice batch_cond_supported
     accepts: the (trial, point) items of about `batch` at a time (whole
     trials) through Context.batch_cond; batch=0, or another lattice: each item
-    through occupy / label / conductance.  cur_rule=None: CUR_MATLAB, the
+    through occupy / label / conductance.  device_shuffle=True (where the batch
+    path runs, ignored otherwise): the group's orders shuffled on the device
+    from the seeds (perc_batch_cond_seeded), the same results bit for bit.
+    cur_rule=None: CUR_MATLAB, the
     reference's pairing.  The dot order is the context's (ctx).  Returns
     (trials, stats): per trial dict(ii, seed | sseed, bseed, rows) with one row
     per grid point (ps, [pb,] nsites, [nbonds,] gbot, gtop, iter, spanning),
@@ -898,16 +983,22 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
             ss, bs = trial_seeds(master, max(numtrials, 1)), None
         batched = batch > 0 and npts > 0 and batch_cond_supported(kind, ctx.lattice, ctx.m, ctx.n, ctx.pbc)
         group = max(1, batch // max(npts, 1)) if batched else 1
+        seeded = batched and device_shuffle and _device_shuffle_ok(ctx, kind)
         stats = np.zeros(npts * 5)
         acc = L.lib().perc_stats_accumulate
         out = []
         for i0 in range(0, numtrials, group):
             tr = range(i0, min(i0 + group, numtrials))
-            so = np.stack([shuffled_ids(t, int(ss[ii])) for ii in tr])
-            bo = np.stack([shuffled_ids(nb, int(bs[ii])) for ii in tr]) if mixed else None
+            if seeded:
+                so = bo = None
+                src = dict(site_seeds=ss[tr.start:tr.stop], bond_seeds=bs[tr.start:tr.stop] if mixed else None)
+            else:
+                so = np.stack([shuffled_ids(t, int(ss[ii])) for ii in tr])
+                bo = np.stack([shuffled_ids(nb, int(bs[ii])) for ii in tr]) if mixed else None
+                src = dict(site_orders=so, bond_orders=bo)
             if batched:
                 it = np.repeat(np.arange(len(tr), dtype=np.int32), npts)
-                res = ctx.batch_cond(kind, it, site_orders=so, bond_orders=bo,
+                res = ctx.batch_cond(kind, it, **src,
                                      item_nsites=np.tile(cnt_s, len(tr)),
                                      item_nbonds=np.tile(cnt_b, len(tr)) if mixed else None,
                                      cur_rule=cur_rule, Va=Va, g0=g0, leak=LEAK, itol=2, tol=tol,

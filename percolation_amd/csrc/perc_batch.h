@@ -74,11 +74,15 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
 // as perc_batch_cond takes them, the orders uploaded by batch_upload_orders /
 // batch_upload_site_orders
 int batch_upload_site_orders(perc_ctx* h, int ntrials, const int* site_orders);
+// A NULL order list the kind reads stands for its seeds (perc_batch_cond_seeded:
+// the ranks came from dev_shuffle_run): the replay regenerates that trial's
+// order with perc_shuffle_seeded.
 int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_orders,
                          const int* bond_orders, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_nbonds, int solve, bool replay,
                          double Va, double g0, double leak, int itol, double tol, int itmax,
-                         perc_batch_item* out);
+                         perc_batch_item* out, const int* site_seeds = nullptr,
+                         const int* bond_seeds = nullptr);
 // ---- threshold scans (perc_batch_scan.hip: k_batch_scan) ----------------
 // sites of the largest lattice one workgroup scans (128 x 128)
 constexpr int kScanSites = 16384;
@@ -112,6 +116,32 @@ hipError_t dev_scan_upload_run(perc_ctx* h, int kind, int scan, int ntrials, con
 void dev_scan_free(perc_ctx* h);
 // the rank arrays dev_batch_upload left on the device (NULL before one)
 const int* dev_batch_ranks(perc_ctx* h, int* ntrials);
+// the same for the site ranks dev_batch_upload_sites left
+const int* dev_batch_site_ranks(perc_ctx* h, int* ntrials);
+// ---- device shuffle (perc_batch_shuffle.hip: k_shuffle_ranks) -----------
+// Byte offsets of k_shuffle_ranks' LDS arena (every offset a multiple of 16):
+// the order (16-bit ids, N + 1) at 0, the swap targets of 64 steps (int).
+struct ShuffleLds {
+  int oJ, total;
+};
+ShuffleLds shuffle_lds(int N);
+// host-only check of perc_shuffle_device_supported: every id of 1..N and the
+// spill slot in 16 bits, the arena within a workgroup's LDS
+bool shuffle_supported(int N);
+// The bond (list PERC_BOND, ntrials x nb) or site (PERC_SITE, ntrials x t)
+// rank buffer of the batch path sized for ntrials trials and marked as
+// holding them, for a kernel to fill: what dev_batch_upload /
+// dev_batch_upload_sites do, without the copy.
+hipError_t dev_batch_reserve(perc_ctx* h, int list, int ntrials, int** d_rank);
+// ntrials trials of that list shuffled by seeds (host) into the reserved
+// buffer; orders_out (host, ntrials x (N + 1)) and ranks_out (host, ntrials x
+// N) may be NULL.  list kShuffleFree: a list of nfree ids that is no list of
+// the lattice, its ranks in a buffer of the shuffle's own (the batch rank
+// buffers stay as they are).
+constexpr int kShuffleFree = -1;
+hipError_t dev_shuffle_run(perc_ctx* h, int list, int ntrials, const int* seeds, int* orders_out,
+                           int* ranks_out, int nfree = 0);
+void dev_shuffle_free(perc_ctx* h);
 // host side (perc_batch_host.cpp): the first spanning bond count of every
 // trial of the group batch_upload_orders uploaded (bond kind), one launch
 int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out);

@@ -508,6 +508,32 @@ const int* dev_batch_ranks(perc_ctx* h, int* ntrials) {
   return B ? B->d_rank : nullptr;
 }
 
+const int* dev_batch_site_ranks(perc_ctx* h, int* ntrials) {
+  BatchState* B = static_cast<BatchState*>(h->batch);
+  *ntrials = B ? B->ntrials_s : 0;
+  return B ? B->d_rank_s : nullptr;
+}
+
+hipError_t dev_batch_reserve(perc_ctx* h, int list, int ntrials, int** d_rank) {
+  BatchState* B = batch_state(h);
+  const bool bonds = list == PERC_BOND;
+  int** p = bonds ? &B->d_rank : &B->d_rank_s;
+  size_t* cap = bonds ? &B->rank_cap : &B->rank_s_cap;
+  int* have = bonds ? &B->ntrials : &B->ntrials_s;
+  const size_t n = (size_t)ntrials * (size_t)(bonds ? h->nb : h->g.t);
+  *have = 0;
+  if (*cap < n) {
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    HIP_TRY(dmalloc(p, n));
+    *cap = n;
+  }
+  *have = ntrials;
+  *d_rank = *p;
+  return hipSuccess;
+}
+
 hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank) {
   BatchState* B = batch_state(h);
   B->ntrials = 0;

@@ -1,6 +1,8 @@
 // perc_batch_host.cpp -- host side of the batch path (include/perc.h:
 // perc_batch_supported, perc_batch_bondc, perc_batch_cond_supported,
-// perc_batch_cond, perc_scan_supported, perc_batch_scan): argument checks, the orders' inverse permutations, the
+// perc_batch_cond, perc_scan_supported, perc_batch_scan and the seeded forms
+// perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded):
+// argument checks, the orders' inverse permutations, the
 // launch geometry and LDS layouts, the fold of the terminal currents and the
 // single-path replay of the items several clusters span.
 #include <hip/hip_runtime.h>
@@ -101,6 +103,19 @@ bool scan_supported(const Geom& g) {
   return scan_lds(g).total + kScanLdsStatic <= kBatchLdsMax;
 }
 
+ShuffleLds shuffle_lds(int N) {
+  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
+  ShuffleLds L{};
+  L.oJ = up16(2 * ((long long)N + 1));
+  L.total = L.oJ + 64 * (int)sizeof(int);
+  return L;
+}
+
+bool shuffle_supported(int N) {
+  if (N < 1 || N > 0xFFFF - 1) return false;  // ids 1..N and the target N + 1 in 16 bits
+  return shuffle_lds(N).total <= kBatchLdsMax;
+}
+
 // rank[tr * N + id - 1] = position of id in trial tr's order of N + 1 entries
 // (the spill slot 0 takes a position and is no element; INT_MAX: absent)
 static void order_ranks(int ntrials, int N, const int* orders, int* rank) {
@@ -155,7 +170,7 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
                          const int* bond_orders, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_nbonds, int solve, bool replay,
                          double Va, double g0, double leak, int itol, double tol, int itmax,
-                         perc_batch_item* out) {
+                         perc_batch_item* out, const int* site_seeds, const int* bond_seeds) {
   const int nb = (int)h->nb, m = h->g.m, t = h->g.t;
   const int rule = kind;  // (PERC_RULE_* of a kind has the kind's number)
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
@@ -167,7 +182,7 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
   const int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
   std::vector<BatchOut> bo((size_t)std::min(nitems, chunk));
   std::vector<double> iout(solve ? bo.size() * 2 * (size_t)m : 0);
-  std::vector<int> slist, blist;
+  std::vector<int> slist, blist, sregen, bregen;
   for (int i0 = 0; i0 < nitems; i0 += chunk) {
     const int n = std::min(chunk, nitems - i0);
     e = dev_batch_run(h, kind, cur_rule, n, item_trial + i0, need_s ? item_nsites + i0 : nullptr,
@@ -192,12 +207,22 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
         const int tr = item_trial[i0 + i];
         const int *ssrc = nullptr, *bsrc = nullptr;
         int slen = 0, blen = 0;
-        if (need_s && !occupy_prefix(site_orders + (size_t)tr * (t + 1), item_nsites[i0 + i], t, &slist,
-                                     &ssrc, &slen))
-          return PERC_EINVAL;
-        if (need_b && !occupy_prefix(bond_orders + (size_t)tr * (nb + 1), item_nbonds[i0 + i], nb, &blist,
-                                     &bsrc, &blen))
-          return PERC_EINVAL;
+        const int* so = need_s && site_orders ? site_orders + (size_t)tr * (t + 1) : nullptr;
+        const int* bo = need_b && bond_orders ? bond_orders + (size_t)tr * (nb + 1) : nullptr;
+        if (need_s && !so) {  // the seeded call: this trial's order, on the host
+          if (!site_seeds) return PERC_EINVAL;
+          sregen.resize((size_t)t + 1);
+          perc_shuffle_seeded(site_seeds[tr], t, sregen.data());
+          so = sregen.data();
+        }
+        if (need_b && !bo) {
+          if (!bond_seeds) return PERC_EINVAL;
+          bregen.resize((size_t)nb + 1);
+          perc_shuffle_seeded(bond_seeds[tr], nb, bregen.data());
+          bo = bregen.data();
+        }
+        if (need_s && !occupy_prefix(so, item_nsites[i0 + i], t, &slist, &ssrc, &slen)) return PERC_EINVAL;
+        if (need_b && !occupy_prefix(bo, item_nbonds[i0 + i], nb, &blist, &bsrc, &blen)) return PERC_EINVAL;
         perc_label_info li{};
         int rc = perc_occupy(h, kind, slen, ssrc, blen, bsrc);
         if (!rc) rc = perc_label(h, &li, nullptr);
@@ -305,13 +330,16 @@ int perc_batch_cond_supported(int kind, int lattice, int m, int n, int pbc) {
   return batch_supported(make_geom(lattice, m, n, pbc), kind) ? 1 : 0;
 }
 
-int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, const int* site_orders,
-                    const int* bond_orders, int nitems, const int* item_trial, const int* item_nsites,
-                    const int* item_nbonds, int solve, double Va, double g0, double leak, int itol,
-                    double tol, int itmax, perc_batch_item* out) {
+// perc_batch_cond (seeded = false: site_src / bond_src are order lists) and
+// perc_batch_cond_seeded (true: seed lists, the orders shuffled on the device)
+static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, int rule, int cur_rule,
+                           int ntrials, const int* site_src, const int* bond_src, int nitems,
+                           const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                           int solve, double Va, double g0, double leak, int itol, double tol, int itmax,
+                           perc_batch_item* out) {
   if (!h) return PERC_EINVAL;
-  auto bad = [](const char* text) {
-    set_error(std::string("perc_batch_cond: ") + text);
+  auto bad = [who](const char* text) {
+    set_error(std::string(who) + ": " + text);
     return PERC_EINVAL;
   };
   const bool pair = (kind == PERC_BOND && rule == PERC_RULE_BOND) ||
@@ -328,8 +356,8 @@ int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, 
   if (!batch_supported(h->g, kind))
     return bad("lattice not supported by the batch kernel for this kind (perc_batch_cond_supported)");
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
-  if (ntrials && ((need_s && !site_orders) || (need_b && !bond_orders)))
-    return bad("an order list the kind reads is missing");
+  if (ntrials && ((need_s && !site_src) || (need_b && !bond_src)))
+    return bad(seeded ? "a seed list the kind reads is missing" : "an order list the kind reads is missing");
   if (nitems && (!item_trial || !out || (need_s && !item_nsites) || (need_b && !item_nbonds)))
     return bad("item_trial, out or a count list the kind reads is missing");
   const int t = h->g.t, nb = (int)h->nb;
@@ -338,12 +366,83 @@ int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, 
     if (need_s && (item_nsites[i] < 0 || item_nsites[i] > t + 1)) return bad("item_nsites outside 0..t+1");
     if (need_b && (item_nbonds[i] < 0 || item_nbonds[i] > nb + 1)) return bad("item_nbonds outside 0..nb+1");
   }
+  if (seeded && ((need_s && !shuffle_supported(t)) || (need_b && !shuffle_supported(nb))))
+    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
   if (nitems == 0) return PERC_OK;
-  int rc = need_b ? batch_upload_orders(h, ntrials, bond_orders) : PERC_OK;
-  if (!rc && need_s) rc = batch_upload_site_orders(h, ntrials, site_orders);
+  if (seeded) {
+    hipSetDevice(h->device);
+    if (need_b) {
+      const hipError_t e = dev_shuffle_run(h, PERC_BOND, ntrials, bond_src, nullptr, nullptr);
+      if (e != hipSuccess) return hip_status(e, who);
+    }
+    if (need_s) {
+      const hipError_t e = dev_shuffle_run(h, PERC_SITE, ntrials, site_src, nullptr, nullptr);
+      if (e != hipSuccess) return hip_status(e, who);
+    }
+    return batch_run_items_kind(h, kind, cur_rule, nullptr, nullptr, nitems, item_trial, item_nsites,
+                                item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, site_src,
+                                bond_src);
+  }
+  int rc = need_b ? batch_upload_orders(h, ntrials, bond_src) : PERC_OK;
+  if (!rc && need_s) rc = batch_upload_site_orders(h, ntrials, site_src);
   if (rc) return rc;
-  return batch_run_items_kind(h, kind, cur_rule, site_orders, bond_orders, nitems, item_trial, item_nsites,
+  return batch_run_items_kind(h, kind, cur_rule, site_src, bond_src, nitems, item_trial, item_nsites,
                               item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out);
+}
+
+int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, const int* site_orders,
+                    const int* bond_orders, int nitems, const int* item_trial, const int* item_nsites,
+                    const int* item_nbonds, int solve, double Va, double g0, double leak, int itol,
+                    double tol, int itmax, perc_batch_item* out) {
+  return batch_cond_impl("perc_batch_cond", false, h, kind, rule, cur_rule, ntrials, site_orders,
+                         bond_orders, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
+                         itol, tol, itmax, out);
+}
+
+int perc_batch_cond_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials,
+                           const int* site_seeds, const int* bond_seeds, int nitems,
+                           const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                           int solve, double Va, double g0, double leak, int itol, double tol, int itmax,
+                           perc_batch_item* out) {
+  return batch_cond_impl("perc_batch_cond_seeded", true, h, kind, rule, cur_rule, ntrials, site_seeds,
+                         bond_seeds, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
+                         itol, tol, itmax, out);
+}
+
+int perc_shuffle_device_supported(int N) { return shuffle_supported(N) ? 1 : 0; }
+
+int perc_batch_shuffle(perc_ctx* h, int list, int ntrials, const int* seeds, int* orders_out,
+                       int* ranks_out) {
+  if (!h) return PERC_EINVAL;
+  auto bad = [](const char* text) {
+    set_error(std::string("perc_batch_shuffle: ") + text);
+    return PERC_EINVAL;
+  };
+  if (list != PERC_BOND && list != PERC_SITE) return bad("list PERC_BOND or PERC_SITE only");
+  if (ntrials < 0) return bad("ntrials < 0");
+  const long long N = list == PERC_BOND ? h->nb : (long long)h->g.t;
+  if (N > INT_MAX || !shuffle_supported((int)N))
+    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (ntrials == 0) return PERC_OK;
+  if (!seeds) return bad("seeds missing");
+  hipSetDevice(h->device);
+  return hip_status(dev_shuffle_run(h, list, ntrials, seeds, orders_out, ranks_out), "perc_batch_shuffle");
+}
+
+int perc_batch_shuffle_n(perc_ctx* h, int N, int ntrials, const int* seeds, int* orders_out,
+                         int* ranks_out) {
+  if (!h) return PERC_EINVAL;
+  auto bad = [](const char* text) {
+    set_error(std::string("perc_batch_shuffle_n: ") + text);
+    return PERC_EINVAL;
+  };
+  if (ntrials < 0) return bad("ntrials < 0");
+  if (!shuffle_supported(N)) return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (ntrials == 0) return PERC_OK;
+  if (!seeds) return bad("seeds missing");
+  hipSetDevice(h->device);
+  return hip_status(dev_shuffle_run(h, kShuffleFree, ntrials, seeds, orders_out, ranks_out, N),
+                    "perc_batch_shuffle_n");
 }
 
 int perc_scan_supported(int lattice, int m, int n, int pbc) {
@@ -352,59 +451,76 @@ int perc_scan_supported(int lattice, int m, int n, int pbc) {
   return scan_supported(make_geom(lattice, m, n, pbc)) ? 1 : 0;
 }
 
-int perc_batch_scan(perc_ctx* h, int kind, int scan, int ntrials, const int* site_orders,
-                    const int* bond_orders, const int* fixed, perc_scan_item* out) {
+// perc_batch_scan (seeded = false: site_src / bond_src are order lists) and
+// perc_batch_scan_seeded (true: seed lists, the orders shuffled on the device)
+static int batch_scan_impl(const char* who, bool seeded, perc_ctx* h, int kind, int scan, int ntrials,
+                           const int* site_src, const int* bond_src, const int* fixed,
+                           perc_scan_item* out) {
   if (!h) return PERC_EINVAL;
-  if (!scan_supported(h->g)) {
-    set_error("perc_batch_scan: lattice not supported by the scan kernel (perc_scan_supported)");
+  auto bad = [who](const char* text) {
+    set_error(std::string(who) + ": " + text);
     return PERC_EINVAL;
-  }
-  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND) {
-    set_error("perc_batch_scan: kind PERC_BOND, PERC_SITE or PERC_SITEBOND only");
-    return PERC_EINVAL;
-  }
-  if (kind == PERC_SITEBOND && scan != PERC_BOND && scan != PERC_SITE) {
-    set_error("perc_batch_scan: scan PERC_BOND or PERC_SITE only");
-    return PERC_EINVAL;
-  }
-  if (ntrials < 0) {
-    set_error("perc_batch_scan: ntrials < 0");
-    return PERC_EINVAL;
-  }
-  if (ntrials == 0) return PERC_OK;
+  };
+  if (!scan_supported(h->g)) return bad("lattice not supported by the scan kernel (perc_scan_supported)");
+  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND)
+    return bad("kind PERC_BOND, PERC_SITE or PERC_SITEBOND only");
+  if (kind == PERC_SITEBOND && scan != PERC_BOND && scan != PERC_SITE)
+    return bad("scan PERC_BOND or PERC_SITE only");
+  if (ntrials < 0) return bad("ntrials < 0");
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
-  if ((need_s && !site_orders) || (need_b && !bond_orders) || !out) {
-    set_error("perc_batch_scan: an order list the kind reads (or out) is missing");
-    return PERC_EINVAL;
-  }
   const int t = h->g.t, nb = (int)h->nb;
+  if (seeded && ((need_s && !shuffle_supported(t)) || (need_b && !shuffle_supported(nb))))
+    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (ntrials == 0) return PERC_OK;
+  if ((need_s && !site_src) || (need_b && !bond_src) || !out)
+    return bad(seeded ? "a seed list the kind reads (or out) is missing"
+                      : "an order list the kind reads (or out) is missing");
   if (kind == PERC_SITEBOND) {
-    if (!fixed) {
-      set_error("perc_batch_scan: PERC_SITEBOND needs fixed[ntrials]");
-      return PERC_EINVAL;
-    }
+    if (!fixed) return bad("PERC_SITEBOND needs fixed[ntrials]");
     const int cap = scan == PERC_BOND ? t : nb;
     for (int i = 0; i < ntrials; ++i)
-      if (fixed[i] < 0 || fixed[i] > cap) {
-        set_error("perc_batch_scan: fixed outside 0..t (scan PERC_BOND) / 0..nb (scan PERC_SITE)");
-        return PERC_EINVAL;
-      }
+      if (fixed[i] < 0 || fixed[i] > cap)
+        return bad("fixed outside 0..t (scan PERC_BOND) / 0..nb (scan PERC_SITE)");
   }
   hipSetDevice(h->device);
   // launches whose rank arrays stay under 64 MB of device memory
   const long long per = 4LL * ((need_s ? t : 0) + (need_b ? nb : 0));
   const int chunk = (int)std::max(1LL, std::min<long long>(ntrials, (64LL << 20) / per));
-  std::vector<int> rank_s(need_s ? (size_t)chunk * t : 0), rank_b(need_b ? (size_t)chunk * nb : 0);
+  std::vector<int> rank_s(need_s && !seeded ? (size_t)chunk * t : 0);
+  std::vector<int> rank_b(need_b && !seeded ? (size_t)chunk * nb : 0);
   for (int i0 = 0; i0 < ntrials; i0 += chunk) {
     const int k = std::min(chunk, ntrials - i0);
-    if (need_s) order_ranks(k, t, site_orders + (size_t)i0 * (t + 1), rank_s.data());
-    if (need_b) order_ranks(k, nb, bond_orders + (size_t)i0 * (nb + 1), rank_b.data());
-    const hipError_t e = dev_scan_upload_run(h, kind, scan, k, need_s ? rank_s.data() : nullptr,
-                                             need_b ? rank_b.data() : nullptr,
-                                             kind == PERC_SITEBOND ? fixed + i0 : nullptr, out + i0);
-    if (e != hipSuccess) return hip_status(e, "perc_batch_scan");
+    const int* fx = kind == PERC_SITEBOND ? fixed + i0 : nullptr;
+    hipError_t e = hipSuccess;
+    if (seeded) {
+      // the chunk's ranks straight into the batch path's buffers, the scan over them
+      if (need_s) e = dev_shuffle_run(h, PERC_SITE, k, site_src + i0, nullptr, nullptr);
+      if (e == hipSuccess && need_b) e = dev_shuffle_run(h, PERC_BOND, k, bond_src + i0, nullptr, nullptr);
+      int have_s = 0, have_b = 0;
+      const int* d_s = need_s ? dev_batch_site_ranks(h, &have_s) : nullptr;
+      const int* d_b = need_b ? dev_batch_ranks(h, &have_b) : nullptr;
+      if (e == hipSuccess) e = dev_scan_run(h, kind, scan, k, d_s, d_b, fx, out + i0);
+    } else {
+      if (need_s) order_ranks(k, t, site_src + (size_t)i0 * (t + 1), rank_s.data());
+      if (need_b) order_ranks(k, nb, bond_src + (size_t)i0 * (nb + 1), rank_b.data());
+      e = dev_scan_upload_run(h, kind, scan, k, need_s ? rank_s.data() : nullptr,
+                              need_b ? rank_b.data() : nullptr, fx, out + i0);
+    }
+    if (e != hipSuccess) return hip_status(e, who);
   }
   return PERC_OK;
+}
+
+int perc_batch_scan(perc_ctx* h, int kind, int scan, int ntrials, const int* site_orders,
+                    const int* bond_orders, const int* fixed, perc_scan_item* out) {
+  return batch_scan_impl("perc_batch_scan", false, h, kind, scan, ntrials, site_orders, bond_orders, fixed,
+                         out);
+}
+
+int perc_batch_scan_seeded(perc_ctx* h, int kind, int scan, int ntrials, const int* site_seeds,
+                           const int* bond_seeds, const int* fixed, perc_scan_item* out) {
+  return batch_scan_impl("perc_batch_scan_seeded", true, h, kind, scan, ntrials, site_seeds, bond_seeds,
+                         fixed, out);
 }
 
 }  // extern "C"

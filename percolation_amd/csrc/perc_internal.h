@@ -272,6 +272,7 @@ struct perc_ctx {
   perc::MarchKnobs knobs;  // as the current dev_solve / dev_bench read them
   void* batch = nullptr;   // perc_batch_bondc's device buffers (perc_batch.hip), made on first use
   void* scan = nullptr;    // perc_batch_scan's device buffers (perc_batch_scan.hip), made on first use
+  void* shuffle = nullptr; // perc_batch_shuffle's device buffers (perc_batch_shuffle.hip), made on first use
 };
 
 namespace perc {

@@ -18,13 +18,16 @@
 ! as-built bs_perc, a host replay) the GPU bisections of `batch` trials at a
 ! time run in one perc_batch_scan call, one workgroup each; the records and
 ! the stdout lines are the same, in trial order.  batch = 0 (default): one
-! perc_first_spanning_mixed call per trial.
+! perc_first_spanning_mixed call per trial.  With dshuffle = 1 beside a
+! batch > 0 in force both orders of those trials are shuffled on the device
+! from sseed / bseed (perc_batch_scan_seeded): no order arrays here, the same
+! records.  dshuffle = 0 (default): the host shuffle.
 !
 ! Parameters: the reference's blocks (sb: 50x50, seed 8811064, ps 0.59 +
 ! 0.01 i x 42 (triangular 0.50 + 0.01 i x 51), iter 100; bs: 10x10, seed
 ! 229102, pb 0.30 + 0.01 i x 71, iter 1000), overridable by sb_perc.nml /
 ! bs_perc.nml (&mixed_scan_nml lattice, m, n, pbc, seed, pstart, pstep,
-! npoints, iters, as_built, device, batch /).
+! npoints, iters, as_built, device, batch, dshuffle /).
 program perc_mixed_scan
   use perc_api
   implicit none
@@ -34,16 +37,17 @@ program perc_mixed_scan
 #ifndef PERC_SCAN_BS
 #define PERC_SCAN_BS 0
 #endif
-  integer(c_int) :: lattice, m, n, pbc, seed, npoints, iters, device, batch
+  integer(c_int) :: lattice, m, n, pbc, seed, npoints, iters, device, batch, dshuffle
   double precision :: pstart, pstep
   logical :: as_built
   namelist /mixed_scan_nml/ lattice, m, n, pbc, seed, pstart, pstep, npoints, iters, as_built, &
-                            device, batch
-  integer(c_int) :: t, nb, ii, jj, fixed, first, pseed(100), sseed(1000), bseed(1000)
+                            device, batch, dshuffle
+  integer(c_int) :: t, nb, ii, jj, fixed, first, pseed(100)
+  integer(c_int), target :: sseed(1000), bseed(1000)
   integer(c_int) :: j0, k, g, scan
   integer(c_int), allocatable, target :: sorder(:), border(:), sorders(:, :), borders(:, :), fx(:)
   type(perc_scan_item), allocatable, target :: items(:)
-  logical :: batched
+  logical :: batched, seeded
   double precision :: pt, ps, pb
   character(len=16) :: nml, out
   type(c_ptr) :: h
@@ -54,6 +58,7 @@ program perc_mixed_scan
   as_built = .true.
   device = 0
   batch = 0
+  dshuffle = 0
   if (PERC_SCAN_BS == 1) then
     m = 10
     n = 10
@@ -91,6 +96,7 @@ program perc_mixed_scan
   t = m * n
   nb = perc_nbonds(lattice, m, n, pbc)
   allocate(sorder(t + 1), border(nb + 1))
+  seeded = .false.
   call perc_trial_seeds(seed, 100, pseed)
   call perc_check(perc_ctx_create(device, lattice, m, n, pbc, h), 'perc_ctx_create')
   open(unit=10, file=trim(out))
@@ -98,7 +104,10 @@ program perc_mixed_scan
   if (batched) batched = perc_scan_supported(lattice, m, n, pbc) == 1
   if (batched) then
     g = min(batch, iters)
-    allocate(sorders(t + 1, g), borders(nb + 1, g), fx(g), items(g))
+    seeded = dshuffle == 1 .and. perc_shuffle_device_supported(t) == 1 .and. &
+             perc_shuffle_device_supported(nb) == 1
+    allocate(fx(g), items(g))
+    if (.not. seeded) allocate(sorders(t + 1, g), borders(nb + 1, g))
   end if
   do ii = 1, npoints
     pt = pstart + (pstep * (ii - 1))
@@ -118,12 +127,17 @@ program perc_mixed_scan
       fx = fixed
       do j0 = 1, iters, g
         k = min(g, iters - j0 + 1)
-        do jj = 1, k
-          call perc_shuffled_ids(t, sseed(j0 + jj - 1), sorders(:, jj))
-          call perc_shuffled_ids(nb, bseed(j0 + jj - 1), borders(:, jj))
-        end do
-        call perc_check(perc_batch_scan(h, PERC_SITEBOND, scan, k, c_loc(sorders), c_loc(borders), &
-                        c_loc(fx), c_loc(items)), 'perc_batch_scan')
+        if (seeded) then
+          call perc_check(perc_batch_scan_seeded(h, PERC_SITEBOND, scan, k, c_loc(sseed(j0)), &
+                          c_loc(bseed(j0)), c_loc(fx), c_loc(items)), 'perc_batch_scan_seeded')
+        else
+          do jj = 1, k
+            call perc_shuffled_ids(t, sseed(j0 + jj - 1), sorders(:, jj))
+            call perc_shuffled_ids(nb, bseed(j0 + jj - 1), borders(:, jj))
+          end do
+          call perc_check(perc_batch_scan(h, PERC_SITEBOND, scan, k, c_loc(sorders), c_loc(borders), &
+                          c_loc(fx), c_loc(items)), 'perc_batch_scan')
+        end if
         do jj = 1, k
           first = items(jj)%first
           if (PERC_SCAN_BS == 1) then

@@ -315,6 +315,43 @@ module perc_api
       integer(c_int), value :: kind, scan, ntrials
     end function perc_batch_scan
 
+    ! host-only: 1 when the shuffle kernel can take a list of nn ids
+    integer(c_int) function perc_shuffle_device_supported(nn) &
+        bind(C, name='perc_shuffle_device_supported')
+      import :: c_int
+      integer(c_int), value :: nn
+    end function perc_shuffle_device_supported
+
+    ! the reference shuffle of one trial per seed on the device (list PERC_BOND
+    ! / PERC_SITE), the ranks left for the batch kernels; orders_out(nn + 1,
+    ! ntrials) and ranks_out(nn, ntrials) may be c_null_ptr
+    integer(c_int) function perc_batch_shuffle(h, list, ntrials, seeds, orders_out, ranks_out) &
+        bind(C, name='perc_batch_shuffle')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h, seeds, orders_out, ranks_out
+      integer(c_int), value :: list, ntrials
+    end function perc_batch_shuffle
+
+    ! perc_batch_scan with site_seeds(ntrials) / bond_seeds(ntrials) in place of
+    ! the orders: shuffled on the device
+    integer(c_int) function perc_batch_scan_seeded(h, kind, scan, ntrials, site_seeds, bond_seeds, &
+        fixed, out) bind(C, name='perc_batch_scan_seeded')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h, site_seeds, bond_seeds, fixed, out
+      integer(c_int), value :: kind, scan, ntrials
+    end function perc_batch_scan_seeded
+
+    ! perc_batch_cond with seeds in place of the orders; item_trial, the count
+    ! lists and out (perc_batch_item records) as pointers
+    integer(c_int) function perc_batch_cond_seeded(h, kind, rule, cur_rule, ntrials, site_seeds, &
+        bond_seeds, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak, itol, tol, &
+        itmax, out) bind(C, name='perc_batch_cond_seeded')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h, site_seeds, bond_seeds, item_trial, item_nsites, item_nbonds, out
+      integer(c_int), value :: kind, rule, cur_rule, ntrials, nitems, solve, itol, itmax
+      real(c_double), value :: Va, g0, leak, tol
+    end function perc_batch_cond_seeded
+
     integer(c_int) function perc_ensemble_bond_cond(e, ntrials, tseed, npts, nbarr, Va, g0, &
         tol, itmax, nrows, gbot, gtop, iters, bf_c, perccln, stats) &
         bind(C, name='perc_ensemble_bond_cond')

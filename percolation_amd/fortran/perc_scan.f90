@@ -16,11 +16,14 @@
 ! `batch` trials at a time are shuffled on the host and one perc_batch_scan
 ! call bisects them all, one workgroup each; the records and the stdout
 ! lines are the same, in trial order.  batch = 0 (default): the loop above.
+! With dshuffle = 1 beside batch > 0 the group's orders are shuffled on the
+! device from the seeds (perc_batch_scan_seeded): no order arrays here, the
+! same records.  dshuffle = 0 (default): the host shuffle.
 !
 ! Parameters: the reference's block (50x50, numtrials 10 for bond_perc /
 ! 1000 for site_perc, master seed 58302), overridable by bond_perc.nml /
 ! site_perc.nml (&perc_scan_nml lattice, m, n, pbc, numtrials, seed, device,
-! batch /).
+! batch, dshuffle /).
 program perc_scan
   use perc_api
   implicit none
@@ -30,12 +33,13 @@ program perc_scan
 #ifndef PERC_SCAN_SITE
 #define PERC_SCAN_SITE 0
 #endif
-  integer(c_int) :: lattice, m, n, pbc, numtrials, seed, device, batch
-  namelist /perc_scan_nml/ lattice, m, n, pbc, numtrials, seed, device, batch
+  integer(c_int) :: lattice, m, n, pbc, numtrials, seed, device, batch, dshuffle
+  namelist /perc_scan_nml/ lattice, m, n, pbc, numtrials, seed, device, batch, dshuffle
   integer(c_int) :: kind, nn, ii, first, cnt, perccls, maxcs, spansz, i0, k, g
   integer(c_int), allocatable, target :: tseed(:), order(:), orders(:, :)
   type(perc_scan_item), allocatable, target :: items(:)
   type(c_ptr) :: sp, bp
+  logical :: seeded
   character(len=16) :: nml, out
   real :: f
   type(c_ptr) :: h
@@ -48,6 +52,7 @@ program perc_scan
   seed = 58302
   device = 0
   batch = 0
+  dshuffle = 0
   if (PERC_SCAN_SITE == 1) then
     kind = PERC_SITE
     numtrials = 1000
@@ -77,21 +82,34 @@ program perc_scan
   open(unit=10, file=trim(out))
   if (batch > 0 .and. perc_scan_supported(lattice, m, n, pbc) == 1) then
     g = min(batch, numtrials)
-    allocate(orders(nn + 1, g), items(g))
-    sp = c_null_ptr
-    bp = c_null_ptr
-    if (kind == PERC_BOND) then
-      bp = c_loc(orders)
-    else
-      sp = c_loc(orders)
-    end if
+    seeded = dshuffle == 1 .and. perc_shuffle_device_supported(nn) == 1
+    allocate(items(g))
+    if (.not. seeded) allocate(orders(nn + 1, g))
     do i0 = 1, numtrials, g
       k = min(g, numtrials - i0 + 1)
-      do ii = 1, k
-        call perc_shuffled_ids(nn, tseed(i0 + ii - 1), orders(:, ii))
-      end do
-      call perc_check(perc_batch_scan(h, kind, PERC_BOND, k, sp, bp, c_null_ptr, c_loc(items)), &
-                      'perc_batch_scan')
+      sp = c_null_ptr
+      bp = c_null_ptr
+      if (seeded) then
+        ! the group's seeds stand for its orders
+        if (kind == PERC_BOND) then
+          bp = c_loc(tseed(i0))
+        else
+          sp = c_loc(tseed(i0))
+        end if
+        call perc_check(perc_batch_scan_seeded(h, kind, PERC_BOND, k, sp, bp, c_null_ptr, &
+                        c_loc(items)), 'perc_batch_scan_seeded')
+      else
+        if (kind == PERC_BOND) then
+          bp = c_loc(orders)
+        else
+          sp = c_loc(orders)
+        end if
+        do ii = 1, k
+          call perc_shuffled_ids(nn, tseed(i0 + ii - 1), orders(:, ii))
+        end do
+        call perc_check(perc_batch_scan(h, kind, PERC_BOND, k, sp, bp, c_null_ptr, c_loc(items)), &
+                        'perc_batch_scan')
+      end if
       do ii = 1, k
         cnt = items(ii)%first
         if (cnt == 0) cnt = nn

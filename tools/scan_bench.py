@@ -14,12 +14,16 @@ Prints one JSON line per workload: trials/s and the per-trial split.
   python tools/scan_bench.py [--L 256,1024 --trials 8 --cond-L 64,256 --cond-trials 2]
 
 With --batch N (lattices perc_scan_supported accepts) each bond_perc /
-site_perc workload is timed twice in the same process, the shuffles
-included, --reps times in alternation: the per-trial path above and the
-batch path (the orders of N trials at a time shuffled on the host, one
-perc_batch_scan call per group: one workgroup bisects each trial).  Prints
-both trials/s (medians), their ratio and whether the two paths' records agree;
-bond_cond is not run.
+site_perc workload is timed three times in the same process, the shuffles
+included, --reps times in alternation: the per-trial path above, the batch
+path (the orders of N trials at a time shuffled on the host, one
+perc_batch_scan call per group: one workgroup bisects each trial) and the
+seeded batch path (the same groups through perc_batch_scan_seeded: the orders
+shuffled on the device, one wave per trial, no host shuffle and no upload).
+Prints the three trials/s (medians), the ratios, every repetition's seconds
+and whether the three paths' records agree; bond_cond is not run.
+--no-per-trial leaves the per-trial leg out (sweeps of --batch for the
+crossover of the two batch legs).
 
   python tools/scan_bench.py --L 50 --trials 1000 --batch 256
 """
@@ -66,11 +70,13 @@ def scan(api, L_mod, lat, L_, kind, trials):
                 mean_first_fraction=round(float(np.mean(firsts)) / N, 5))
 
 
-def scan_ab(api, L_mod, lat, L_, kind, trials, batch, reps):
-    """the per-trial path and the batch path on the same trials, alternating"""
+def scan_ab(api, L_mod, lat, L_, kind, trials, batch, reps, per_trial_leg=True):
+    """the per-trial path, the batch path and the seeded batch path on the
+    same trials, alternating"""
     N = api.nbonds(lat, L_, L_, 0) if kind == L_mod.BOND else L_ * L_
     seeds = api.trial_seeds(58302, trials, scale=1000000)
     key = "bond_orders" if kind == L_mod.BOND else "site_orders"
+    skey = "bond_seeds" if kind == L_mod.BOND else "site_seeds"
 
     def per_trial(ctx):
         out = []
@@ -89,30 +95,48 @@ def scan_ab(api, L_mod, lat, L_, kind, trials, batch, reps):
             out += [(r["first"], r["maxcs"], r["span_size"]) for r in ctx.batch_scan(kind, **{key: orders})]
         return out, t_shuf
 
+    def seeded(ctx):
+        out = []
+        for i0 in range(0, trials, batch):
+            res = ctx.batch_scan_seeded(kind, **{skey: seeds[i0:i0 + batch]})
+            out += [(r["first"], r["maxcs"], r["span_size"]) for r in res]
+        return out
+
     with api.Context(lat, L_, L_, 0) as ctx:
         warm = api.shuffled_ids(N, 12345)
         api.first_spanning(ctx, warm, kind, N)  # warm-up of both paths
         ctx.cluster_sizes()
         ctx.batch_scan(kind, **{key: np.stack([warm] * min(batch, trials))})
-        ta, tb, ts = [], [], []
+        ctx.batch_scan_seeded(kind, **{skey: seeds[:min(batch, trials)]})
+        ta, tb, tc, ts = [], [], [], []
+        ra = None
         for _ in range(reps):
             t0 = time.perf_counter()
-            ra = per_trial(ctx)
+            if per_trial_leg:
+                ra = per_trial(ctx)
             t1 = time.perf_counter()
             rb, shuf = batched(ctx)
             t2 = time.perf_counter()
+            rc = seeded(ctx)
+            t3 = time.perf_counter()
             ta.append(t1 - t0)
             tb.append(t2 - t1)
+            tc.append(t3 - t2)
             ts.append(shuf)
-    wa, wb = float(np.median(ta)), float(np.median(tb))
+    wa, wb, wc = float(np.median(ta)), float(np.median(tb)), float(np.median(tc))
     return dict(workload="%s_perc %s L=%d" % ("bond" if kind == L_mod.BOND else "site",
                                                "square" if lat == 0 else "triangular", L_),
                 trials=trials, batch=batch, reps=reps,
-                per_trial_trials_per_s=round(trials / wa, 2), batch_trials_per_s=round(trials / wb, 2),
-                ratio=round(wa / wb, 2),
-                per_trial_s=[round(x, 4) for x in ta], batch_s=[round(x, 4) for x in tb],
+                per_trial_trials_per_s=round(trials / wa, 2) if per_trial_leg else None,
+                batch_trials_per_s=round(trials / wb, 2),
+                seeded_trials_per_s=round(trials / wc, 2),
+                ratio=round(wa / wb, 2) if per_trial_leg else None,
+                seeded_ratio=round(wb / wc, 2),
+                per_trial_s=[round(x, 4) for x in ta] if per_trial_leg else None,
+                batch_s=[round(x, 4) for x in tb], seeded_s=[round(x, 4) for x in tc],
+                seeded_beats_batch=max(tc) < min(tb),
                 batch_host_shuffle_s=round(float(np.median(ts)), 4),
-                records_equal=ra == rb,
+                records_equal=(ra is None or ra == rb) and rb == rc,
                 mean_first_fraction=round(float(np.mean([r[0] for r in rb])) / N, 5))
 
 
@@ -140,6 +164,7 @@ def main():
     ap.add_argument("--batch", type=int, default=0,
                     help="A/B of the per-trial path and perc_batch_scan with this many trials per call")
     ap.add_argument("--reps", type=int, default=3, help="alternating repetitions of the A/B")
+    ap.add_argument("--no-per-trial", action="store_true", help="with --batch: the two batch legs only")
     args = ap.parse_args()
     from percolation_amd import _lib as L_mod
     from percolation_amd import api
@@ -149,7 +174,7 @@ def main():
                 raise SystemExit("L=%d: not a lattice perc_scan_supported accepts" % L_)
             for kind in (L_mod.BOND, L_mod.SITE):
                 print(json.dumps(scan_ab(api, L_mod, 0, L_, kind, args.trials, args.batch,
-                                         args.reps)), flush=True)
+                                         args.reps, not args.no_per_trial)), flush=True)
         return
     for L_ in map(int, args.L.split(",")):
         for kind in (L_mod.BOND, L_mod.SITE):

@@ -468,7 +468,9 @@ int perc_set_march_rows(perc_ctx *h, int rows);
    row-major q-storing march.  (Round 4 removed the variants that lost their
    A/Bs: workgroup row-march 4, deferred reductions 32, persistent march
    256, the strip-major march past the Infinity Cache 1024; those bits are
-   rejected.) */
+   rejected.  Round 6 re-measured the deferred reductions as an opt-in
+   variant, 0.1515-0.1527 against 0.1511 ms per iteration with the
+   collectors, and they were removed again.) */
 #define PERC_MARCH_QFREE 1
 #define PERC_MARCH_ALT 2
 #define PERC_SOLVE_RESIDENT 8
@@ -528,7 +530,7 @@ int perc_set_dot_order(perc_ctx *h, int order);
 #define PERC_RAN_TAG 32       /* tagged-granule reductions */
 #define PERC_RAN_HOST_FOLD 64 /* PERC_DOT_LITERAL_HOST: the sums folded by the host */
 #define PERC_RAN_XCD_GROUPED 128 /* resident solve: XCD-grouped reductions (else the flat all-gather) */
-#define PERC_RAN_DEFERRED 256 /* march: each launch's totals formed by the next launch (no collector tail) */
+/* (bit 256 of out4[1] is retired -- it marked the deferred reductions -- and is not to be reused) */
 int perc_last_solve(perc_ctx *h, int *out4);
 /* err of every iteration of the last solve (linbcg's per-iteration
    `write (*,*) iter, err`, bondc.f:834): min(cap, iterations) values into

@@ -85,19 +85,9 @@ struct CGArgs {
   // the march's u16-code kernels take the interior form's scalar path too
   int sqcls;
   int* merr;
-  // deferred reductions of the strip-major tagged march (k_cg_march DEF):
-  // 1 = a launch only publishes its workgroups' granules and the NEXT launch
-  // forms the totals itself (B: q.p -> ak; P: z.r, r.r -> bk, err, stop;
-  // k_march_epi after each chunk of launches), 2 = the same kernels in
-  // perc_bench_kernel's fixed-iteration probe (no stop, no scalars but bkn),
-  // 0 = collectors at the end of each launch; mnwg = the grid both march
-  // kernels run
-  int mdef;
-  int mnwg;
-  int mdsc1;  // deferred totals read the granules with sc1 loads (else plain, through L2)
   int rm_pnib;  // the row-major march P reads the nibble codes too (else the u16 codes)
   // strip-major q-free march, x on the two electrode-side rows only (the
-  // fast order, no deferred totals): B(k + 1) applies iteration k's x +=
+  // fast order): B(k + 1) applies iteration k's x +=
   // ak(k) p(k) to those rows at its start, k_march_xpend the last one
   int mxin;
   // strip-major march: {p(k), z = r/d} of every strip's first and last
@@ -1112,9 +1102,6 @@ CGArgs make_cg_args(perc_ctx* h) {
   a.sqcls = h->nib_ok && !h->g.pbc ? 1 : 0;
   for (int c = 0; c < 3; ++c) a.ncls[c] = a.sqcls ? h->ncls[c] : 0u;
   a.merr = nullptr;
-  a.mdef = 0;
-  a.mnwg = 0;
-  a.mdsc1 = 0;
   a.rm_pnib = 0;
   a.mxin = 0;
   a.ez = nullptr;

@@ -65,10 +65,6 @@ struct CGScalars {
   int done;      // set once err <= tol or iter > itmax
   int pad[3];
   double part[4];  // row slabs: this slab's raw partials (q.p, z.r, r.r, ||D^-1 b||^2)
-  // deferred march reductions (CGArgs::mdef): bkn[j & 1] = bknum of
-  // iteration j (j >= 1; iteration 0's is bknum above), parity-buffered so
-  // a launch reads the previous value while its writer stores the new one
-  double bkn[2];
   // ak of the previous iteration (the march P's collector keeps it when it
   // forms the new ak): B(k + 1) applies x += ak(k) p(k) at its start (CGArgs::mxin)
   double akprev;
@@ -170,9 +166,6 @@ struct KernelTiming {
 struct MarchKnobs {
   bool rm_pu16 = false;    // PERC_MARCH_RM_PU16: the row-major march P on the u16 codes, not the nibble codes
   bool edge_step = false;  // PERC_MARCH_EDGE_STEP: B stores its edge pairs per step, not staged in LDS
-  bool nodef = false;      // PERC_MARCH_NODEF: PERC_MARCH_DEF ignored
-  int def = 0;             // PERC_MARCH_DEF=<kDefP | kDefB bits>: deferred reductions (opt-in)
-  bool def_sc1 = false;    // PERC_MARCH_DEF_SC1: the deferred totals' loads past L2
   bool xafter = false;     // PERC_MARCH_XAFTER: x updated after each B's walk, not at the next B's start
   bool res_flat = false;   // PERC_RES_FLAT: the resident solve's flat all-gather reductions
   int time_every = 64;     // PERC_TIME_EVERY=<n>: kernel timing samples every n-th iteration of a

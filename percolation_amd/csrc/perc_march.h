@@ -107,11 +107,11 @@ __device__ __forceinline__ void gran_poll_n(__amdgpu_buffer_rsrc_t rg, const int
   }
 }
 
-constexpr int kDefGroups = 12;  // groups of kGroup workgroups a deferred total takes (grid <= 768)
+constexpr int kFlatGroups = 12;  // groups of kGroup workgroups the one-hop collector takes (grid <= 768)
 
-// One-hop collector (grids of <= kDefGroups groups, the default; the
-// two-level collectors below with PERC_MARCH_GROUPCOL, A/B probe builds
-// only): the last logical workgroup polls every workgroup granule itself --
+// One-hop collector (grids of <= kFlatGroups groups; larger grids take the
+// two-level collectors below): the last logical workgroup polls every
+// workgroup granule itself --
 // wave w the granules of groups w, w + 4, w + 8, each lane re-polling only
 // the granules it has not yet seen -- and forms the totals by the two-level
 // association: a group's granules summed by one wave_sum over its lanes in
@@ -122,9 +122,9 @@ constexpr int kDefGroups = 12;  // groups of kGroup workgroups a deferred total 
 template <int NV>
 __device__ __forceinline__ void flat_collect(__amdgpu_buffer_rsrc_t rg, int nwg, int ngroups, double tag, int* err,
                                              double (&tot)[NV], double* s_red) {
-  __shared__ double s_grp[NV * kDefGroups];
+  __shared__ double s_grp[NV * kFlatGroups];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  constexpr int kPer = kDefGroups / 4;  // groups per wave (4 waves per workgroup)
+  constexpr int kPer = kFlatGroups / 4;  // groups per wave (4 waves per workgroup)
   double val[kPer][NV];
   bool need[kPer][NV];
 #pragma unroll
@@ -174,7 +174,7 @@ __device__ __forceinline__ void flat_collect(__amdgpu_buffer_rsrc_t rg, int nwg,
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
         const double w = wave_sum(val[i][j]);  // the group collector's sum
-        if (lane == 0) s_grp[j * kDefGroups + g] = w;
+        if (lane == 0) s_grp[j * kFlatGroups + g] = w;
       }
     }
   }
@@ -183,7 +183,7 @@ __device__ __forceinline__ void flat_collect(__amdgpu_buffer_rsrc_t rg, int nwg,
 #pragma unroll
   for (int j = 0; j < NV; ++j) {  // the last collector's thread-strided group sums
     acc[j] = 0.0;
-    if ((int)threadIdx.x < ngroups) acc[j] = acc[j] + s_grp[j * kDefGroups + threadIdx.x];
+    if ((int)threadIdx.x < ngroups) acc[j] = acc[j] + s_grp[j * kFlatGroups + threadIdx.x];
   }
   block_sum<NV>(acc, s_red);
   if (threadIdx.x == 0)
@@ -194,22 +194,19 @@ __device__ __forceinline__ void flat_collect(__amdgpu_buffer_rsrc_t rg, int nwg,
   for (int j = 0; j < NV; ++j) tot[j] = s_red[16 + j];
 }
 
-// Fixed collectors instead of tickets (the default; PERC_MARCH_TICKETS, A/B
-// probe builds only: the ticket form below): a group's LAST logical
+// Fixed collectors instead of tickets: a group's LAST logical
 // workgroup (lb = g0 + gn - 1, dispatched late: logical blocks of an XCD are
 // consecutive) sums its group's granules as they arrive and publishes the
 // group's granule; the last group's collector sums the group granules.  The
-// association is the ticket form's term for term (the group's lanes in
-// order + butterfly; the groups thread-strided + block sum), so every value
-// is bitwise the same; what goes is the two agent-scope ticket atomics (and
-// their resets) on the tail's critical path: the collectors only poll.
+// association is publish_and_reduce's ticket form term for term (the group's
+// lanes in order + butterfly; the groups thread-strided + block sum), so every
+// value is bitwise the same; what goes is the two agent-scope ticket atomics
+// (and their resets) on the tail's critical path: the collectors only poll
+// (tickets in the tagged protocol itself: bitwise the same and 0.3 % slower,
+// profiles/r5_23_*).
 template <int NV>
-__device__ bool publish_and_reduce_tagged(double (&v)[NV], double* gran, unsigned* tickets, int lb,
-                                          int nwg, double tag, int* err, double (&tot)[NV],
-                                          double* s_red, int* s_flag) {
-#if !defined(PERC_MARCH_TICKETS)
-  (void)tickets;
-  (void)s_flag;
+__device__ bool publish_and_reduce_tagged(double (&v)[NV], double* gran, int lb, int nwg, double tag, int* err,
+                                          double (&tot)[NV], double* s_red) {
   block_sum<NV>(v, s_red);
   const int ngroups = red_groups(nwg);
   const int grp = lb / kGroup, g0 = grp * kGroup, gn = min(kGroup, nwg - g0);
@@ -221,13 +218,11 @@ __device__ bool publish_and_reduce_tagged(double (&v)[NV], double* gran, unsigne
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, make_double2(v[j], tag)), rg,
                                              (j * nwg + lb) * 16, 0, 16);
   }
-#if !defined(PERC_MARCH_GROUPCOL)
-  if (ngroups <= kDefGroups) {  // (uniform) the one-hop collector
+  if (ngroups <= kFlatGroups) {  // (uniform) the one-hop collector
     if (lb != nwg - 1) return false;
     flat_collect<NV>(rg, nwg, ngroups, tag, err, tot, s_red);
     return true;
   }
-#endif
   if (lb != g0 + gn - 1) return false;  // (uniform) not a collector
   if (threadIdx.x < 64) {  // the group's collector: wave 0 sums the group's partials
     const int lane = threadIdx.x;
@@ -271,212 +266,10 @@ __device__ bool publish_and_reduce_tagged(double (&v)[NV], double* gran, unsigne
 #pragma unroll
   for (int j = 0; j < NV; ++j) tot[j] = s_red[16 + j];
   return true;
-#else
-  block_sum<NV>(v, s_red);
-  const int ngroups = red_groups(nwg);
-  const int grp = lb / kGroup, g0 = grp * kGroup, gn = min(kGroup, nwg - g0);
-  // granules: [j][workgroup] then [j][group]
-  const __amdgpu_buffer_rsrc_t rg = rsrc(gran, (unsigned)(NV * (nwg + ngroups) * 16));
-  const int goff = NV * nwg;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, make_double2(v[j], tag)), rg,
-                                             (j * nwg + lb) * 16, 0, 16);
-    const unsigned tk = __hip_atomic_fetch_add(&tickets[grp * kTicketStride], 1u,
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_flag[0] = tk == (unsigned)(gn - 1);
-  }
-  __syncthreads();
-  if (!s_flag[0]) return false;
-  if (threadIdx.x < 64) {  // last of its group: wave 0 sums the group's partials
-    const int lane = threadIdx.x;
-    double w[NV];
-    if (lane < gn) {
-      int off[NV];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) off[j] = (j * nwg + g0 + lane) * 16;
-      gran_poll_n<NV>(rg, off, tag, err, w);
-    } else {
-#pragma unroll
-      for (int j = 0; j < NV; ++j) w[j] = 0.0;
-    }
-#pragma unroll
-    for (int j = 0; j < NV; ++j) w[j] = wave_sum(w[j]);
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < NV; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, make_double2(w[j], tag)), rg,
-                                               (goff + j * ngroups + grp) * 16, 0, 16);
-      __hip_atomic_store(&tickets[grp * kTicketStride], 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned tk = __hip_atomic_fetch_add(&tickets[ngroups * kTicketStride], 1u,
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_flag[1] = tk == (unsigned)(ngroups - 1);
-    }
-  }
-  __syncthreads();
-  if (!s_flag[1]) return false;
-  double acc[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) acc[j] = 0.0;
-  for (int i = threadIdx.x; i < ngroups; i += blockDim.x) {
-    int off[NV];
-    double v[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) off[j] = (goff + j * ngroups + i) * 16;
-    gran_poll_n<NV>(rg, off, tag, err, v);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) acc[j] = acc[j] + v[j];
-  }
-  __syncthreads();  // s_red reuse
-  block_sum<NV>(acc, s_red);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s_red[16 + j] = acc[j];
-    __hip_atomic_store(&tickets[ngroups * kTicketStride], 0u, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NV; ++j) tot[j] = s_red[16 + j];
-  return true;
-#endif
-}
-
-// Deferred reductions (DEF, an opt-in variant of the strip-major tagged
-// march, PERC_MARCH_DEF; measured and not the default, perc_solve.hip
-// setup_granules): a launch ends once its workgroups have published their
-// granules -- no collector waits on the slowest workgroup's granule and no
-// second hop follows (the march trace put the exits 2.9 us (P) and 4.4 us
-// (B) past the last walk, profiles/r5_4_mtrace_summary_L4096.txt; the
-// launch times moved by 1.4 and 2.3 us).  The NEXT launch forms the totals
-// in every workgroup, after its first rows' loads are issued: the group
-// sums by the same lanes-in-order wave_sum the group collectors formed and
-// the group totals by the same thread-strided block_sum the last collector
-// formed, so every total is the collector form's bitwise in every
-// workgroup (tagged = ticket = deferred: test_tagged_reduction_is_bitwise_
-// the_ticket_one).  The granules are complete when a launch starts (the
-// previous one has ended); their tags are checked, not polled.
-// CGArgs::mdef bits: kDefP -- P publishes only, B forms q.p (ak) at its
-// start; kDefB -- B publishes only, the next P (and k_march_epi) forms z.r,
-// r.r (bk, err, stop); kDefBench -- perc_bench_kernel's fixed iteration (no
-// stop, no scalars but bkn)
-constexpr int kDefP = 1, kDefB = 2, kDefBench = 4;
-template <int NV>
-__device__ __forceinline__ void def_totals(const double* gran, int nwg, double tag, int* err,
-                                           double (&tot)[NV], double* s_red, double* s_grp, bool sc1) {
-  const int ngroups = red_groups(nwg);
-  const __amdgpu_buffer_rsrc_t rg = rsrc(gran, (unsigned)(NV * (nwg + ngroups) * 16));
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  constexpr int kPer = kDefGroups / 4;  // groups per wave (4 waves per workgroup)
-  double2 g2[kPer][NV];
-#pragma unroll
-  for (int i = 0; i < kPer; ++i) {  // every load issued before any is used
-    const int g = wid + 4 * i, g0 = g * kGroup, gn = g < ngroups ? min(kGroup, nwg - g0) : 0;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int off = (int)(lane < gn ? (j * nwg + g0 + lane) * 16 : kOOB);
-      // (sc1: past this XCD's L2; plain: the XCD's workgroups share one L2
-      // fill -- the previous launch's write-through granules are in memory
-      // when this launch starts, and a stale line would fail the tag check)
-      g2[i][j] = __builtin_bit_cast(double2, sc1 ? __builtin_amdgcn_raw_buffer_load_b128(rg, off, 0, 16)
-                                                 : __builtin_amdgcn_raw_buffer_load_b128(rg, off, 0, 0));
-    }
-  }
-  bool bad = false;
-#pragma unroll
-  for (int i = 0; i < kPer; ++i) {
-    const int g = wid + 4 * i;
-    if (g < ngroups) {  // (wave-uniform)
-      const int gn = min(kGroup, nwg - g * kGroup);
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        bad = bad || (lane < gn && g2[i][j].y != tag);
-        const double w = wave_sum(lane < gn ? g2[i][j].x : 0.0);  // the group collector's sum
-        if (lane == 0) s_grp[j * kDefGroups + g] = w;
-      }
-    }
-  }
-  if (err && __any(bad) && lane == 0) *err = 1;
-  __syncthreads();
-  double acc[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {  // the last collector's thread-strided group sums
-    acc[j] = 0.0;
-    if ((int)threadIdx.x < ngroups) acc[j] = acc[j] + s_grp[j * kDefGroups + threadIdx.x];
-  }
-  block_sum<NV>(acc, s_red);
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s_red[16 + j] = acc[j];
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NV; ++j) tot[j] = s_red[16 + j];
-  __syncthreads();  // s_red / s_grp reuse
-}
-
-// a workgroup-uniform double held in SGPRs (values read back from LDS land
-// in VGPRs: 2 more for the whole walk -- P's 169 instead of 167, 2 waves
-// per SIMD instead of 3)
-__device__ __forceinline__ double sgpr_double(double v) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-// B(kk)'s epilogue, deferred to the next P (or k_march_epi): the z.r and
-// r.r totals -> bk, err, the stop test (k_cg_b's epilogue; linbcg
-// bondc.f:785-787, 834).  Every workgroup forms the same values; `writer`
-// stores them.  bkn is parity-buffered: the writer stores bknum(kk) while
-// the others read bknum(kk - 1).  Returns the stop decision.
-__device__ __forceinline__ bool march_def_epilogue(const CGArgs& a, int kk, const double (&tb)[2], bool writer,
-                                                   double& bk) {
-  CGScalars* S = a.S;
-  const double old = kk == 1 ? S->bknum : S->bkn[(kk - 1) & 1];
-  const double err = sqrt(tb[1]) / S->bnrm;
-  bk = tb[0] / old;
-  const bool live = !(a.mdef & kDefBench);
-  const bool dn = live && (!(err > S->tol) || kk >= S->itmax + 1);
-  if (writer) {
-    S->bkn[kk & 1] = tb[0];
-    if (live) {
-      S->bk = bk;
-      S->err = err;
-      if (kk - 1 < a.err_hist_cap) a.err_hist[kk - 1] = err;
-      S->iter = kk;
-      if (dn) S->done = 1;
-    }
-  }
-  return dn;
 }
 
 // (kMarchW columns per wave strip, kMarchWaves strips per workgroup, the
 // edge-staging depths kEdgeRows / kEdgeRowsRm: perc_bands.h)
-// A/B probe builds only: the column-class path in the row-major march too
-// (PERC_MARCH_RM_SQ), optionally held to 4 waves per SIMD (PERC_MARCH_RM_SQ4)
-#if defined(PERC_MARCH_RM_SQ) || defined(PERC_MARCH_RM_SQ4)
-constexpr bool kMarchRmSq = true;
-#else
-constexpr bool kMarchRmSq = false;
-#endif
-// the row-major march's nibble codes (on unless PERC_MARCH_RM_U16, A/B probe
-// builds only)
-#ifdef PERC_MARCH_RM_U16
-constexpr bool kMarchRmNib = false;
-#else
-constexpr bool kMarchRmNib = true;
-#endif
-// waves per SIMD the row-major nibble march (B) is held to (its column-class
-// path would take 132-134 VGPRs: 3 waves; 128 without spills when held;
-// the u16 march has 123-126)
-#if defined(PERC_MARCH_RM_SQ4)
-#define PERC_MARCH_MINW(SM, MODE, PK) ((SM) || (MODE) == 0 ? 1 : 4)
-#elif defined(PERC_MARCH_RM_NOBOUND)  // (A/B probe builds only)
-#define PERC_MARCH_MINW(SM, MODE, PK) 1
-#else
-#define PERC_MARCH_MINW(SM, MODE, PK) (!(SM) && (PK) && (MODE) != 0 ? 4 : 1)
-#endif
 
 struct MRow {       // one prefetched row of the lane's pair (+ halo column)
   double2 p, r;     // p(k-1), r
@@ -706,11 +499,7 @@ __device__ __forceinline__ void march_load(const CGArgs& a, const MGeom& g, cons
     const unsigned eh = rowok ? melem<SM>(a, B, gr, g.hcol) : 0u;
     const unsigned o8 = rowok ? e * 8u : kOOB;
     const bool rown = MODE != kMarchB || (gr >= g.r0 && gr < g.rend);
-#if defined(PERC_PROBE_NO_PHALO)  // (A/B probe builds only: P's halo-column loads' cost, wrong values)
-    const bool hk = rowok && g.hok && MODE == kMarchB;
-#else
     const bool hk = rowok && g.hok;
-#endif
     const unsigned h8 = hk ? eh * 8u : kOOB;
     if constexpr (PK) {
       // the pair's two slot nibbles in one byte (element e even); the count
@@ -857,7 +646,7 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
     if constexpr (PK && !SM) sqp = true;
 #endif
     else if constexpr (PK) sqp = !a.T.pbc;
-    else if constexpr (SM || kMarchRmSq) sqp = a.sqcls && !__any((((c0w ^ g.cb0) | (c1w ^ g.cb1)) >> 8) != 0u);
+    else if constexpr (SM) sqp = a.sqcls && !__any((((c0w ^ g.cb0) | (c1w ^ g.cb1)) >> 8) != 0u);
     else sqp = false;
     if (sqp) {
       // Open square lattice, nibble codes: every row is interior, column 0
@@ -1056,17 +845,16 @@ __device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, cons
 // TR: phase probe -- lane 0 of every wave stores {kernel entry, walk end,
 // exit, hardware id} wall-clock stamps (100 MHz) into a.mtrace[4 w ..]
 // TAG: the epilogue reductions by tagged granules (publish_and_reduce_tagged)
-// DEF: deferred reductions (with TAG, strip-major, fast order; see def_totals)
 // ESR > 0: B's edge pairs staged in LDS (ESR rows per side) and stored
 // after the walk -- bands of <= ESR rows: kEdgeRows strip-major, kEdgeRowsRm
 // on the row-major march's 8-row bands (the host picks it, CGArgs::mes)
+// Waves per SIMD: the row-major nibble march (P and B) is held to 4 (its
+// column-class path would take 132-134 VGPRs: 3 waves; 128 without spills
+// when held; the u16 march has 123-126)
+constexpr int march_min_waves(int mode, bool sm, bool pk) { return !sm && pk && mode != kMarchPQ ? 4 : 1; }
 template <int MODE, bool SM = false, int D = kMarchDepth, int PAUX = 0, bool TR = false,
-          bool TAG = false, bool PK = false, bool LIT = false, bool DEF = false, int ESR = 0>
-// (the deferred instantiations are held to 3 waves per SIMD -- 168 VGPRs:
-// the strip-major march's slot-weighted bands assume 3 resident workgroups
-// per CU, and their totals code left P at 169 without the bound)
-__global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MODE, PK)) void k_cg_march(CGArgs a) {
-  static_assert(!DEF || (TAG && SM && !LIT), "deferred reductions: the tagged strip-major fast march");
+          bool TAG = false, bool PK = false, bool LIT = false, int ESR = 0>
+__global__ __launch_bounds__(64 * kMarchWaves, march_min_waves(MODE, SM, PK)) void k_cg_march(CGArgs a) {
   static_assert(ESR == 0 || (MODE == kMarchB && (SM || PK)), "staged edge pairs: the march B with edge pairs");
   const unsigned long long tr_t0 = TR ? wall_clock64() : 0ull;
   unsigned long long tr_t1 = 0ull;
@@ -1146,7 +934,7 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
   g.cb0 = g.cb1 = g.cbh = 0u;
   g.lo0 = g.lo1 = 0xFu;
   g.hi0 = g.hi1 = 0u;
-  if ((PK || a.sqcls) && (SM || kMarchRmSq)) {
+  if ((PK || a.sqcls) && SM) {
     auto cls = [&](int c) { return c == 0 ? a.ncls[1] : (c == m - 1 ? a.ncls[2] : a.ncls[0]); };
     g.cb0 = cls(g.col);
     g.cb1 = cls(g.col + 1);
@@ -1165,7 +953,7 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
   }
   // (B, strip-major, fast order, x on the electrode-side rows: iteration
   // k - 1's x update of those rows, its loads issued behind the ring's)
-  constexpr bool kXin = MODE == kMarchB && SM && !LIT && !DEF;
+  constexpr bool kXin = MODE == kMarchB && SM && !LIT;
   const bool xin = kXin && a.mxin && k > 1 && active;
   double2 xo[2], po[2];
   if constexpr (kXin) {
@@ -1202,35 +990,7 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
   load_dtab(a.St, s_dt);
   __syncthreads();
   double bk = S->bk, ak = S->ak;
-  // bknum of this iteration's ak (P's collector epilogue): the scalar, or
-  // with kDefB the total this launch formed from B(k-1)'s granules
-  double bkn_it = S->bknum;
-  if constexpr (DEF) {
-    // the previous launch's totals, formed here (its first rows' loads are
-    // in flight): B takes P(k)'s q.p -> ak (kDefP); P takes B(k-1)'s z.r and
-    // r.r -> bk, err and the stop test (kDefB)
-    __shared__ double s_grp[2 * kDefGroups];
-    const bool live = !(a.mdef & kDefBench);
-    int* derr = live ? a.merr : nullptr;
-    if (MODE == kMarchB) {
-      if (a.mdef & kDefP) {
-        double tp[1];
-        def_totals<1>(a.mgran, gridDim.x, a.mtag, derr, tp, s_red, s_grp, a.mdsc1 != 0);
-        const double bknum = (a.mdef & kDefB) && k > 1 ? S->bkn[(k - 1) & 1] : S->bknum;
-        ak = sgpr_double(bknum / tp[0]);
-        if (lb == 0 && threadIdx.x == 0 && live) {
-          S->akden = tp[0];
-          S->ak = ak;
-        }
-      }
-    } else if (!first && (a.mdef & kDefB)) {
-      double tb[2];
-      def_totals<2>(a.mgran_b, gridDim.x, a.mtag - 1.0, derr, tb, s_red, s_grp, a.mdsc1 != 0);
-      if (march_def_epilogue(a, k - 1, tb, lb == 0 && threadIdx.x == 0, bk)) return;  // (uniform)
-      bk = sgpr_double(bk);
-      bkn_it = sgpr_double(tb[0]);
-    }
-  }
+  const double bknum = S->bknum;  // of this iteration's ak (P's collector epilogue)
   double acc[2] = {0.0, 0.0};
   if (active) {
     double* s_w = s_win[threadIdx.x >> 6];
@@ -1302,29 +1062,9 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
       a.mtrace[4 * (size_t)w + 3] = ((unsigned long long)xcc << 32) | hw;
     }
   }
-  bool pub_only = false;
-  if constexpr (DEF) pub_only = (a.mdef & (MODE == kMarchB ? kDefB : kDefP)) != 0;
-  if (pub_only) {
-    // publish only: this launch's workgroup partials, {value, tag} granules
-    // written through; the next launch (or k_march_epi) forms the totals
-    constexpr int NV = MODE == kMarchB ? 2 : 1;
-    double v[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = acc[j];
-    block_sum<NV>(v, s_red);
-    if (threadIdx.x == 0) {
-      const int ngroups = red_groups(gridDim.x);
-      double* gran = MODE == kMarchB ? a.mgran_b : a.mgran;
-      const __amdgpu_buffer_rsrc_t rg = rsrc(gran, (unsigned)(NV * ((int)gridDim.x + ngroups) * 16));
-#pragma unroll
-      for (int j = 0; j < NV; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, make_double2(v[j], a.mtag)), rg,
-                                               (j * (int)gridDim.x + lb) * 16, 0, 16);
-    }
-  } else if (MODE != kMarchB) {
+  if (MODE != kMarchB) {
     double v[1] = {acc[0]}, tot[1];
-    const bool last = TAG ? publish_and_reduce_tagged<1>(v, a.mgran, a.tickets, lb, gridDim.x, a.mtag,
-                                                         a.merr, tot, s_red, s_flag)
+    const bool last = TAG ? publish_and_reduce_tagged<1>(v, a.mgran, lb, gridDim.x, a.mtag, a.merr, tot, s_red)
                           : publish_and_reduce<1>(v, a.partials, a.tickets, lb, gridDim.x, tot, s_red, s_flag);
     if (last) {
       if (threadIdx.x == 0) {
@@ -1334,15 +1074,14 @@ __global__ __launch_bounds__(64 * kMarchWaves, DEF ? 3 : PERC_MARCH_MINW(SM, MOD
         } else {
           S->akprev = S->ak;
           S->akden = tot[0];
-          S->ak = bkn_it / tot[0];
+          S->ak = bknum / tot[0];
         }
       }
     }
   } else {
     double tot[2];
     const bool last =
-        TAG ? publish_and_reduce_tagged<2>(acc, a.mgran_b, a.tickets + a.tstride, lb, gridDim.x, a.mtag, a.merr, tot,
-                                           s_red, s_flag)
+        TAG ? publish_and_reduce_tagged<2>(acc, a.mgran_b, lb, gridDim.x, a.mtag, a.merr, tot, s_red)
             : publish_and_reduce<2>(acc, a.partials + a.pstride, a.tickets + a.tstride, lb, gridDim.x,
                                     tot, s_red, s_flag);
     if (last) {
@@ -1389,19 +1128,6 @@ __global__ __launch_bounds__(kBlock) void k_march_xpend(CGArgs a) {
   a.x[row * m + col] = a.x[row * m + col] + S->ak * p[sm_at(a.T, row, col)];
 }
 
-// The deferred epilogue of a chunk's last B (DEF): one workgroup of the
-// march's shape forms the z.r and r.r totals as the next P would and stores
-// iter, err, bk, the stop flag -- the host reads them after each chunk.  The
-// next P forms the same values again (every store idempotent).
-__global__ __launch_bounds__(64 * kMarchWaves) void k_march_epi(CGArgs a) {
-  __shared__ double s_red[32];
-  __shared__ double s_grp[2 * kDefGroups];
-  if (a.S->done) return;
-  double tb[2], bk;
-  def_totals<2>(a.mgran_b, a.mnwg, a.mtag, a.merr, tb, s_red, s_grp, true);
-  march_def_epilogue(a, a.kiter, tb, threadIdx.x == 0, bk);
-}
-
 // ---------------------------------------------------------------------------
 // The march variants: k_cg_march's template arguments as a value, and the
 // list of every instantiation libperc compiles -- the only place one is
@@ -1412,7 +1138,7 @@ struct MarchKey {
   int mode;  // kMarchPQ / kMarchP / kMarchB
   bool sm;   // strip-major layout
   int d, paux;
-  bool tr, tag, pk, lit, def;
+  bool tr, tag, pk, lit;
   int esr;
 };
 using MarchKernel = void (*)(CGArgs);
@@ -1423,67 +1149,59 @@ struct MarchVariant {
 #define PERC_MARCH_ROW(...) MarchVariant{MarchKey{__VA_ARGS__}, k_cg_march<__VA_ARGS__>},
 
 // q-storing P+S: row slabs, modes without QFREE, literal order past 2 GB of terms
-#define PERC_MARCH_PQ kMarchPQ, false, 3, 0, false, false, false, false, false, 0
+#define PERC_MARCH_PQ kMarchPQ, false, 3, 0, false, false, false, false, 0
 // tagged strip-major P on the u16 codes: the kernel whose occupancy sizes the
 // bands (march_rows_for, march_geometry)
-#define PERC_MARCH_OCC kMarchP, true, 3, kNT, false, true, false, false, false, 0
+#define PERC_MARCH_OCC kMarchP, true, 3, kNT, false, true, false, false, 0
 
 // Strip-major rows (the default solve at L <= 4096): 3 rows prefetched,
 // nontemporal last-use loads.  Row-major rows (vectors past the Infinity
 // Cache): kMarchDepth rows, P and B on B's 8-row bands (L = 8192: P 0.314 vs
 // 0.355 ms, r4_8; B's nontemporal r(k) loads 0.300 vs 0.331 ms, r4_3).
-// Columns: MODE, SM, D, PAUX, TR, TAG, PK, LIT, DEF, ESR (k_cg_march's order).
+// Columns: MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR (k_cg_march's order).
 #define PERC_MARCH_VARIANTS(X) \
-  X(PERC_MARCH_PQ)                                                           /* q-storing P+S */ \
-  X(kMarchP, true, 3, kNT, false, false, false, false, false, 0)             /* strip-major P, u16, ticket reduction */ \
-  X(kMarchP, true, 3, kNT, true, false, false, false, false, 0)              /* strip-major P, u16, ticket reduction, phase probe */ \
-  X(PERC_MARCH_OCC)                                                          /* strip-major P, u16, tagged granules */ \
-  X(kMarchP, true, 3, kNT, true, true, false, false, false, 0)               /* strip-major P, u16, tagged granules, phase probe */ \
-  X(kMarchP, true, 3, kNT, false, false, false, true, false, 0)              /* strip-major P, u16, literal order */ \
-  X(kMarchP, true, 3, kNT, false, true, false, true, false, 0)               /* strip-major P, u16, literal order, solve tagged */ \
-  X(kMarchP, true, 3, kNT, false, true, false, false, true, 0)               /* strip-major P, u16, deferred totals (opt-in) */ \
-  X(kMarchP, true, 3, kNT, true, true, false, false, true, 0)                /* strip-major P, u16, deferred totals, phase probe */ \
-  X(kMarchP, true, 3, kNT, false, false, true, false, false, 0)              /* strip-major P, nibble, ticket reduction */ \
-  X(kMarchP, true, 3, kNT, true, false, true, false, false, 0)               /* strip-major P, nibble, ticket reduction, phase probe */ \
-  X(kMarchP, true, 3, kNT, false, true, true, false, false, 0)               /* strip-major P, nibble, tagged granules: the default P */ \
-  X(kMarchP, true, 3, kNT, true, true, true, false, false, 0)                /* strip-major P, nibble, tagged granules, phase probe */ \
-  X(kMarchP, true, 3, kNT, false, false, true, true, false, 0)               /* strip-major P, nibble, literal order */ \
-  X(kMarchP, true, 3, kNT, false, true, true, true, false, 0)                /* strip-major P, nibble, literal order, solve tagged */ \
-  X(kMarchP, true, 3, kNT, false, true, true, false, true, 0)                /* strip-major P, nibble, deferred totals (opt-in) */ \
-  X(kMarchP, true, 3, kNT, true, true, true, false, true, 0)                 /* strip-major P, nibble, deferred totals, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, false, false, false, false, 0)             /* strip-major B, u16, ticket reduction */ \
-  X(kMarchB, true, 3, kNT, true, false, false, false, false, 0)              /* strip-major B, u16, ticket reduction, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, true, false, false, false, 0)              /* strip-major B, u16, tagged granules */ \
-  X(kMarchB, true, 3, kNT, true, true, false, false, false, 0)               /* strip-major B, u16, tagged granules, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, false, false, true, false, 0)              /* strip-major B, u16, literal order */ \
-  X(kMarchB, true, 3, kNT, false, true, false, true, false, 0)               /* strip-major B, u16, literal order, solve tagged */ \
-  X(kMarchB, true, 3, kNT, false, true, false, false, true, 0)               /* strip-major B, u16, deferred totals (opt-in) */ \
-  X(kMarchB, true, 3, kNT, true, true, false, false, true, 0)                /* strip-major B, u16, deferred totals, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, true, false, false, false, kEdgeRows)      /* strip-major B, u16, edge pairs staged in LDS */ \
-  X(kMarchB, true, 3, kNT, true, true, false, false, false, kEdgeRows)       /* strip-major B, u16, staged edge pairs, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, false, true, false, false, 0)              /* strip-major B, nibble, ticket reduction */ \
-  X(kMarchB, true, 3, kNT, true, false, true, false, false, 0)               /* strip-major B, nibble, ticket reduction, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, false, 0)               /* strip-major B, nibble, tagged granules */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, false, 0)                /* strip-major B, nibble, tagged granules, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, false, true, true, false, 0)               /* strip-major B, nibble, literal order */ \
-  X(kMarchB, true, 3, kNT, false, true, true, true, false, 0)                /* strip-major B, nibble, literal order, solve tagged */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, true, 0)                /* strip-major B, nibble, deferred totals (opt-in) */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, true, 0)                 /* strip-major B, nibble, deferred totals, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, false, kEdgeRows)       /* strip-major B, nibble, edge pairs staged in LDS: the default B */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, false, kEdgeRows)        /* strip-major B, nibble, staged edge pairs, phase probe */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, false, false, false, 0)    /* row-major P, u16 */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, false, true, false, 0)     /* row-major P, u16, literal order */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, true, false, false, 0)     /* row-major P, nibble (128 VGPRs unspilled at the 4-wave bound): past the cache */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, true, true, false, 0)      /* row-major P, nibble, literal order */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, false, false, false, 0)  /* row-major B, u16 */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, false, true, false, 0)   /* row-major B, u16, literal order */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, false, 0)   /* row-major B, nibble, edge pairs stored per step */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, true, true, false, 0)    /* row-major B, nibble, literal order */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, false, kEdgeRowsRm) /* row-major B, nibble, edge pairs staged in LDS: past the cache */
+  X(PERC_MARCH_PQ)                                                   /* q-storing P+S */ \
+  X(kMarchP, true, 3, kNT, false, false, false, false, 0)            /* strip-major P, u16, ticket reduction */ \
+  X(kMarchP, true, 3, kNT, true, false, false, false, 0)             /* strip-major P, u16, ticket reduction, phase probe */ \
+  X(PERC_MARCH_OCC)                                                  /* strip-major P, u16, tagged granules */ \
+  X(kMarchP, true, 3, kNT, true, true, false, false, 0)              /* strip-major P, u16, tagged granules, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, false, false, true, 0)             /* strip-major P, u16, literal order */ \
+  X(kMarchP, true, 3, kNT, false, true, false, true, 0)              /* strip-major P, u16, literal order, solve tagged */ \
+  X(kMarchP, true, 3, kNT, false, false, true, false, 0)             /* strip-major P, nibble, ticket reduction */ \
+  X(kMarchP, true, 3, kNT, true, false, true, false, 0)              /* strip-major P, nibble, ticket reduction, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, true, true, false, 0)              /* strip-major P, nibble, tagged granules: the default P */ \
+  X(kMarchP, true, 3, kNT, true, true, true, false, 0)               /* strip-major P, nibble, tagged granules, phase probe */ \
+  X(kMarchP, true, 3, kNT, false, false, true, true, 0)              /* strip-major P, nibble, literal order */ \
+  X(kMarchP, true, 3, kNT, false, true, true, true, 0)               /* strip-major P, nibble, literal order, solve tagged */ \
+  X(kMarchB, true, 3, kNT, false, false, false, false, 0)            /* strip-major B, u16, ticket reduction */ \
+  X(kMarchB, true, 3, kNT, true, false, false, false, 0)             /* strip-major B, u16, ticket reduction, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, true, false, false, 0)             /* strip-major B, u16, tagged granules */ \
+  X(kMarchB, true, 3, kNT, true, true, false, false, 0)              /* strip-major B, u16, tagged granules, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, false, true, 0)             /* strip-major B, u16, literal order */ \
+  X(kMarchB, true, 3, kNT, false, true, false, true, 0)              /* strip-major B, u16, literal order, solve tagged */ \
+  X(kMarchB, true, 3, kNT, false, true, false, false, kEdgeRows)     /* strip-major B, u16, edge pairs staged in LDS */ \
+  X(kMarchB, true, 3, kNT, true, true, false, false, kEdgeRows)      /* strip-major B, u16, staged edge pairs, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, true, false, 0)             /* strip-major B, nibble, ticket reduction */ \
+  X(kMarchB, true, 3, kNT, true, false, true, false, 0)              /* strip-major B, nibble, ticket reduction, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, 0)              /* strip-major B, nibble, tagged granules */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, 0)               /* strip-major B, nibble, tagged granules, phase probe */ \
+  X(kMarchB, true, 3, kNT, false, false, true, true, 0)              /* strip-major B, nibble, literal order */ \
+  X(kMarchB, true, 3, kNT, false, true, true, true, 0)               /* strip-major B, nibble, literal order, solve tagged */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, kEdgeRows)      /* strip-major B, nibble, edge pairs staged in LDS: the default B */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, kEdgeRows)       /* strip-major B, nibble, staged edge pairs, phase probe */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, false, false, 0)   /* row-major P, u16 */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, false, true, 0)    /* row-major P, u16, literal order */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, true, false, 0)    /* row-major P, nibble (128 VGPRs unspilled at the 4-wave bound): past the cache */ \
+  X(kMarchP, false, kMarchDepth, 0, false, false, true, true, 0)     /* row-major P, nibble, literal order */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, false, false, 0) /* row-major B, u16 */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, false, true, 0)  /* row-major B, u16, literal order */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, 0)  /* row-major B, nibble, edge pairs stored per step */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, true, true, 0)   /* row-major B, nibble, literal order */ \
+  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, kEdgeRowsRm) /* row-major B, nibble, edge pairs staged in LDS: past the cache */
 
 constexpr bool operator==(const MarchKey& a, const MarchKey& b) {
   return a.mode == b.mode && a.sm == b.sm && a.d == b.d && a.paux == b.paux && a.tr == b.tr && a.tag == b.tag &&
-         a.pk == b.pk && a.lit == b.lit && a.def == b.def && a.esr == b.esr;
+         a.pk == b.pk && a.lit == b.lit && a.esr == b.esr;
 }
 
 MarchKernel march_pq_kernel() {

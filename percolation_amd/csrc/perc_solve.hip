@@ -89,26 +89,25 @@ void march_occupancy(const perc_ctx* h, int* cus, int* per_cu) {
 // The march kernel of a launch: mode kMarchP for the P side (P of the q-free
 // march, else the q-storing P+S), kMarchB for the q-free B.
 //  strip-major pair (the default solve at L <= 4096; phase probe: a.mtrace):
-//    staged edges (B, a.mes) > deferred > literal > tagged > trace > plain
+//    staged edges (B, a.mes) > literal > tagged > trace > plain
 //  row-major pair (vectors past the Infinity Cache): literal and nibble codes
 //    independently (P's nibble codes: a.rm_pnib), B's staged edges without lit
 MarchKey select_march(int mode, const perc_ctx* h, const CGArgs& a) {
   if (!h->qfree) return MarchKey{PERC_MARCH_PQ};
   const bool lit = a.lit != nullptr, nib = a.nib != nullptr, tag = a.mgran != nullptr, tr = a.mtrace != nullptr;
   if (!a.sm) {
-    if (mode == kMarchP) return {kMarchP, false, kMarchDepth, 0, false, false, nib && a.rm_pnib, lit, false, 0};
-    return {kMarchB, false, kMarchDepth, kNT, false, false, nib, lit, false, !lit && nib && a.mes ? kEdgeRowsRm : 0};
+    if (mode == kMarchP) return {kMarchP, false, kMarchDepth, 0, false, false, nib && a.rm_pnib, lit, 0};
+    return {kMarchB, false, kMarchDepth, kNT, false, false, nib, lit, !lit && nib && a.mes ? kEdgeRowsRm : 0};
   }
-  const MarchKey k = {mode, true, 3, kNT, false, false, nib, false, false, 0};
-  auto with = [k](bool tr, bool tag, bool lit, bool def, int esr) {
+  const MarchKey k = {mode, true, 3, kNT, false, false, nib, false, 0};
+  auto with = [k](bool tr, bool tag, bool lit, int esr) {
     MarchKey v = k;
-    v.tr = tr, v.tag = tag, v.lit = lit, v.def = def, v.esr = esr;
+    v.tr = tr, v.tag = tag, v.lit = lit, v.esr = esr;
     return v;
   };
-  if (mode == kMarchB && a.mes && !lit && !a.mdef && tag) return with(tr, true, false, false, kEdgeRows);
-  if (a.mdef) return with(tr, true, false, true, 0);
-  if (lit) return with(false, tag, true, false, 0);
-  return with(tr, tag, false, false, 0);
+  if (mode == kMarchB && a.mes && !lit && tag) return with(tr, true, false, kEdgeRows);
+  if (lit) return with(false, tag, true, 0);
+  return with(tr, tag, false, 0);
 }
 
 // launch the selected march kernel on its grid (the slot-weighted bands' or
@@ -118,8 +117,8 @@ hipError_t launch_march(perc_ctx* h, int mode, hipStream_t st, const CGArgs& a) 
   const MarchKey k = select_march(mode, h, a);
   const MarchKernel fn = find_march(k);
   if (!fn) {
-    fprintf(stderr, "[perc] march variant {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d} is not compiled\n", k.mode, k.sm, k.d,
-            k.paux, k.tr, k.tag, k.pk, k.lit, k.def, k.esr);
+    fprintf(stderr, "[perc] march variant {%d, %d, %d, %d, %d, %d, %d, %d, %d} is not compiled\n", k.mode, k.sm, k.d,
+            k.paux, k.tr, k.tag, k.pk, k.lit, k.esr);
     return hipErrorInvalidConfiguration;
   }
   klaunch(h, fn, k.sm && a.wslots > 0 ? h->wm_grid : h->march_grid, 64 * kMarchWaves, st, a);
@@ -197,7 +196,7 @@ hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
   hipStream_t st = h->stream;
   h->nib_used = false;
   a.rm_pnib = h->knobs.rm_pu16 ? 0 : 1;
-  if (!kMarchRmNib || !h->nib_ok || !sq_nibble_form(h) || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) ||
+  if (!h->nib_ok || !sq_nibble_form(h) || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) ||
       !h->march || !h->qfree || a.sm)
     return hipSuccess;
   const long long n = (long long)a.T.nrows * a.T.m;
@@ -245,18 +244,6 @@ hipError_t setup_granules(perc_ctx* h, CGArgs& a, int itmax) {
   a.mgran_b = h->d.mgran + region;
   a.merr = &h->d.scal->pad[1];
   ++h->solve_epoch;
-  // deferred reductions (k_cg_march DEF, opt-in: MarchKnobs::def): the fast
-  // order's march, one slab, grids of <= kDefGroups reduction groups.
-  // Measured on the metric (profiles/r6_4_def_ab_*): the
-  // collectors' tails are 1.4 (P) and 2.3 us (B), the totals formed at the
-  // next launch's start cost 1.7 (one sum) and 3.7 us (two): 0.1511 ms per
-  // iteration with the collectors, 0.1515 / 0.1527 / 0.1523 deferred (P's,
-  // B's, both) -- the collectors stay the default
-  const int grid = a.wslots > 0 ? h->wm_grid : h->march_grid;
-  const MarchKnobs& kn = h->knobs;
-  a.mnwg = grid;
-  a.mdef = !a.lit && !a.slab && red_groups(grid) <= kDefGroups && !kn.nodef ? (kn.def & (kDefP | kDefB)) : 0;
-  a.mdsc1 = kn.def_sc1 ? 1 : 0;
   return hipSuccess;
 }
 
@@ -769,9 +756,6 @@ MarchKnobs read_march_knobs() {
   MarchKnobs k;
   k.rm_pu16 = flag("PERC_MARCH_RM_PU16");
   k.edge_step = flag("PERC_MARCH_EDGE_STEP");
-  k.nodef = flag("PERC_MARCH_NODEF");
-  k.def = num("PERC_MARCH_DEF", 0);
-  k.def_sc1 = flag("PERC_MARCH_DEF_SC1");
   k.xafter = flag("PERC_MARCH_XAFTER");
   k.res_flat = flag("PERC_RES_FLAT");
   if (time_every > 0) k.time_every = time_every;  // (else the default)
@@ -792,16 +776,13 @@ hipError_t prepare_march(perc_ctx* h, CGArgs& a, int itmax, bool probe) {
   // next B at its start (k_cg_march, kXin), the last by k_march_xpend
   // (MarchKnobs::xafter: the update after each B's walk; the probe times the
   // production path whatever the knob)
-  a.mxin = a.sm && !a.lit && !a.mdef && !a.slab && a.xrows == h->g.m && !(h->knobs.xafter && !probe) ? 1 : 0;
-  if (probe) {
-    if (a.mdef) a.mdef |= kDefBench;  // the deferred march at a fixed iteration: no stop, no scalars
-    return hipSuccess;
-  }
+  a.mxin = a.sm && !a.lit && !a.slab && a.xrows == h->g.m && !(h->knobs.xafter && !probe) ? 1 : 0;
+  if (probe) return hipSuccess;
   const bool host_fold = a.lit && h->dot_order == PERC_DOT_LITERAL_HOST;
   h->last_flags = (h->dot_order != PERC_DOT_FAST ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0) |
                   (h->march && h->qfree ? PERC_RAN_QFREE : 0) | (a.sm ? PERC_RAN_STRIPS : 0) |
                   (a.nib ? PERC_RAN_NIBBLE : 0) | (a.mgran ? PERC_RAN_TAG : 0) |
-                  (host_fold ? PERC_RAN_HOST_FOLD : 0) | (a.mdef ? PERC_RAN_DEFERRED : 0);
+                  (host_fold ? PERC_RAN_HOST_FOLD : 0);
   return hipSuccess;
 }
 }  // namespace
@@ -1286,10 +1267,6 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
         else k_fold_b<false><<<1, 64, 0, st>>>(a);
         HIP_TRY(dbg_sync(st, "k_fold_b"));
       }
-    }
-    if (a.mdef & kDefB) {  // the chunk's last B: its epilogue, for the host's stop test
-      k_march_epi<<<1, 64 * kMarchWaves, 0, st>>>(a);
-      HIP_TRY(dbg_sync(st, "k_march_epi"));
     }
     launched += chunk;
     e = hipGetLastError();

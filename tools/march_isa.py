@@ -25,7 +25,7 @@ open-square path alone, so the walk loop's count is one step's.
 
   python tools/march_isa.py                       # the four default kernels
   python tools/march_isa.py -D PERC_MARCH_PIN_SQ -D PERC_MARCH_DYNMASK   # the run-time mask (also: PERC_MARCH_FIRST_RT)
-  python tools/march_isa.py --kernel '<1, true, 3, 2, false, true, true, false, false, 0>'
+  python tools/march_isa.py --kernel '<1, true, 3, 2, false, true, true, false, 0>'
   python tools/march_isa.py --asm perc_solve.s    # an assembly file made before
 """
 import argparse
@@ -40,14 +40,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "percolation_amd", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
-# k_cg_march<MODE, SM, D, PAUX, TR, TAG, PK, LIT, DEF, ESR>: the L = 4096
+# k_cg_march<MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR>: the L = 4096
 # pair (strip-major, nibble codes, tagged) and the L = 8192 pair (row-major,
 # nibble codes)
 DEFAULT = [
-    ("strip-major P", r"k_cg_march<1, true, 3, 2, false, true, true, false, false, 0>"),
-    ("strip-major B", r"k_cg_march<2, true, 3, 2, false, true, true, false, false, 64>"),
-    ("row-major nibble P", r"k_cg_march<1, false, 2, 0, false, false, true, false, false, 0>"),
-    ("row-major nibble B", r"k_cg_march<2, false, 2, 2, false, false, true, false, false, 16>"),
+    ("strip-major P", r"k_cg_march<1, true, 3, 2, false, true, true, false, 0>"),
+    ("strip-major B", r"k_cg_march<2, true, 3, 2, false, true, true, false, 64>"),
+    ("row-major nibble P", r"k_cg_march<1, false, 2, 0, false, false, true, false, 0>"),
+    ("row-major nibble B", r"k_cg_march<2, false, 2, 2, false, false, true, false, 16>"),
 ]
 
 CLASSES = ("VALU", "cndmask", "fp64", "SALU", "SMEM", "waits", "LDS", "VMEM")

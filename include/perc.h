@@ -671,6 +671,36 @@ int perc_batch_cond(perc_ctx *h, int kind, int rule, int cur_rule, int ntrials,
                     int solve, double Va, double g0, double leak, int itol,
                     double tol, int itmax, perc_batch_item *out);
 
+/* ---- batch conductance up to 128 x 128 (opt-in) ----------------------- *
+ * perc_batch_bondc / perc_batch_cond stop at 8192 interior rows (about
+ * 90 x 90): their kernel keeps p, q and the row codes of the one-workgroup
+ * solve in LDS.  A second kernel, k_batch_cond_large, keeps p alone there --
+ * 1024 threads, at most 16 rows each, a thread's row codes and r in its
+ * registers, q never in LDS (held in registers between the two passes in
+ * the fast order, rebuilt from p, bitwise the q of q.p, in the literal one),
+ * x on the 2m rows the currents read -- and so takes every lattice of at most
+ * 16384 sites (128 x 128, 64 x 256), the same stages and the same results:
+ * under PERC_DOT_LITERAL bitwise perc_conductance's, under PERC_DOT_FAST
+ * k_batch_cond's tree over 16 rows per thread.  While the flag of
+ * perc_set_batch_large is set on a context, perc_batch_bondc,
+ * perc_batch_cond and perc_batch_cond_seeded run that kernel on every
+ * lattice perc_batch_large_supported accepts for the kind and answer
+ * PERC_EINVAL (the text names perc_batch_large_supported) on any other;
+ * argument rules, chunking, the fallback replay and the item records are
+ * unchanged.  While it is clear (the default) nothing changes.  On a lattice
+ * both kernels take, the default one is the faster. */
+/* host-only: 1 when the large batch kernel can run this kind on this
+   lattice: m, n >= 3, even m on the triangular lattice, m*n <= 16384, every
+   interior row a stencil form with every stencil bond present, and the
+   kind's LDS arena within a workgroup's 160 KB.  Accepts every lattice
+   perc_batch_cond_supported accepts. */
+int perc_batch_large_supported(int kind, int lattice, int m, int n, int pbc);
+/* enable != 0: the context's batch calls run the large kernel; 0: the
+   default kernel again */
+int perc_set_batch_large(perc_ctx *h, int enable);
+/* the flag: 1 or 0 (PERC_EINVAL for a NULL context) */
+int perc_batch_large(perc_ctx *h);
+
 /* ---- batch of small threshold scans (one workgroup each) -------------- *
  * The reference's threshold programs (Fortran/Square/bond_perc.f:204-366,
  * site_perc.f:150-256, sb_perc.f:104-372, bs_perc.f:104-395) are ensembles
@@ -818,6 +848,11 @@ int perc_ensemble_workers(perc_ensemble *e);
    ignored and perc_ensemble_batch returns 0, else it returns items. */
 int perc_ensemble_set_batch(perc_ensemble *e, int items);
 int perc_ensemble_batch(perc_ensemble *e);
+/* perc_set_batch_large on every device's context (enable != 0: the batch
+   path runs the large kernel); while set, perc_ensemble_batch goes by
+   perc_batch_large_supported(PERC_BOND, ..) instead of perc_batch_supported,
+   so the setting of perc_ensemble_set_batch holds up to 128 x 128 */
+int perc_ensemble_set_batch_large(perc_ensemble *e, int enable);
 /* device dev's own context (e.g. for single-trial calls); NULL if out of range */
 perc_ctx *perc_ensemble_ctx(perc_ensemble *e, int dev);
 /* the trials device `dev` of `ndev` runs, 1-based, ascending (ii_out may be

@@ -188,6 +188,10 @@ SIGNATURES = {
     "perc_batch_cond": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP,
                                   _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                   C.c_double, C.c_int, _VP]),
+    "perc_batch_large_supported": (C.c_int, [C.c_int] * 5),
+    "perc_set_batch_large": (C.c_int, [_VP, C.c_int]),
+    "perc_batch_large": (C.c_int, [_VP]),
+    "perc_ensemble_set_batch_large": (C.c_int, [_VP, C.c_int]),
     "perc_scan_supported": (C.c_int, [C.c_int] * 4),
     "perc_batch_scan": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
     "perc_shuffle_device_supported": (C.c_int, [C.c_int]),

@@ -109,6 +109,14 @@ def batch_cond_supported(kind, lattice, m, n, pbc=0):
     return bool(L.lib().perc_batch_cond_supported(int(kind), lattice, m, n, pbc))
 
 
+def batch_large_supported(kind, lattice, m, n, pbc=0):
+    """perc_batch_large_supported (host-only): True when the large batch
+    kernel (Context.set_batch_large) can run this kind on this lattice --
+    m, n >= 3, m * n <= 16384 sites (128 x 128), stencil operator, the kind's
+    LDS arena; every lattice batch_cond_supported accepts."""
+    return bool(L.lib().perc_batch_large_supported(int(kind), lattice, m, n, pbc))
+
+
 KIND_RULE = {L.BOND: L.RULE_BOND, L.SITE: L.RULE_SITE, L.SITEBOND: L.RULE_MIXED}
 
 
@@ -306,6 +314,16 @@ class Context:
         products (perc_set_dot_order; LITERAL reproduces the reference solver
         bitwise)."""
         L.check(L.lib().perc_set_dot_order(self.h, int(order)), "perc_set_dot_order")
+
+    def set_batch_large(self, enable=True):
+        """perc_set_batch_large: batch_bondc / batch_cond on the large kernel
+        (p alone in LDS; lattices up to 128 x 128, batch_large_supported) while
+        set; False: the default batch kernel again."""
+        L.check(L.lib().perc_set_batch_large(self.h, int(bool(enable))), "perc_set_batch_large")
+
+    def batch_large(self):
+        """the flag of set_batch_large (perc_batch_large)"""
+        return bool(L.lib().perc_batch_large(self.h))
 
     def err_history(self):
         """err of every iteration of the last solve (perc_err_history)."""
@@ -937,7 +955,7 @@ def bond_cond_grid(lattice=0, m=10, n=10, pbc=0, master=58302, numtrials=1, Va=1
 
 def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0.9, 1.0), master=58302,
                numtrials=1, batch=256, cur_rule=None, Va=1.0, g0=1.0, tol=1e-8, itmax=2500, ctx=None,
-               device=0, device_shuffle=False):
+               device=0, device_shuffle=False, large=False):
     """The mean conductance curve of site or mixed percolation over trials:
     G(ps) (kind SITE, site.f + ConductCalc.m's site rule; grid a list of ps) or
     G(ps, pb) (kind SITEBOND, sitebond.f + the mixed rule; grid a list of
@@ -952,6 +970,9 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
     through occupy / label / conductance.  device_shuffle=True (where the batch
     path runs, ignored otherwise): the group's orders shuffled on the device
     from the seeds (perc_batch_cond_seeded), the same results bit for bit.
+    large=True: the context's set_batch_large flag set for the call (restored
+    after it) and batch_large_supported in place of batch_cond_supported, so
+    the batch path runs up to 128 x 128.
     cur_rule=None: CUR_MATLAB, the
     reference's pairing.  The dot order is the context's (ctx).  Returns
     (trials, stats): per trial dict(ii, seed | sseed, bseed, rows) with one row
@@ -970,7 +991,10 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
         cur_rule = natural_cur_rule(kind)
     own = ctx is None
     ctx = ctx or Context(lattice, m, n, pbc, device)
+    was_large = ctx.batch_large()
     try:
+        if large:
+            ctx.set_batch_large(True)
         t, nb = ctx.t, ctx.nb
         pts = [(float(p[0]), float(p[1])) if mixed else (float(p), None) for p in grid]
         npts = len(pts)
@@ -980,7 +1004,8 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
             ss, bs = paired_seeds(master, max(numtrials, 1))
         else:
             ss, bs = trial_seeds(master, max(numtrials, 1)), None
-        batched = batch > 0 and npts > 0 and batch_cond_supported(kind, ctx.lattice, ctx.m, ctx.n, ctx.pbc)
+        supported = batch_large_supported if ctx.batch_large() else batch_cond_supported
+        batched = batch > 0 and npts > 0 and supported(kind, ctx.lattice, ctx.m, ctx.n, ctx.pbc)
         group = max(1, batch // max(npts, 1)) if batched else 1
         seeded = batched and device_shuffle and _device_shuffle_ok(ctx, kind)
         stats = np.zeros(npts * 5)
@@ -1034,6 +1059,8 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
     finally:
         if own:
             ctx.close()
+        elif large:
+            ctx.set_batch_large(was_large)
 
 
 # ---------------------------------------------------------------- file output
@@ -1050,7 +1077,7 @@ class Ensemble:
     trials striped ii -> device (ii-1) mod ndev, one RCCL all-reduce of the
     per-grid-point statistics (include/perc.h; Square/bond_cond.f:123-498)."""
 
-    def __init__(self, lattice, m, n, pbc=0, ndev=1, devices=None, workers=1, batch=0):
+    def __init__(self, lattice, m, n, pbc=0, ndev=1, devices=None, workers=1, batch=0, large=False):
         self.lattice, self.m, self.n, self.pbc = lattice, m, n, pbc
         self.nb = nbonds(lattice, m, n, pbc)
         h = C.c_void_p()
@@ -1063,6 +1090,9 @@ class Ensemble:
         if workers != 1:
             self.set_workers(workers)
         self.batch = 0
+        self.large = False
+        if large:
+            self.set_batch_large(True)
         if batch:
             self.set_batch(batch)
 
@@ -1070,8 +1100,17 @@ class Ensemble:
         """about `items` (trial, grid point) realisations per launch of the
         batch kernel in bond_cond (perc_ensemble_set_batch; 0: the per-trial
         loop).  self.batch is what is in force: 0 on a lattice the batch
-        kernel does not support (batch_supported)."""
+        kernel does not support (batch_supported; batch_large_supported
+        after set_batch_large)."""
         L.check(L.lib().perc_ensemble_set_batch(self.h, int(items)), "perc_ensemble_set_batch")
+        self.batch = L.lib().perc_ensemble_batch(self.h)
+
+    def set_batch_large(self, enable=True):
+        """perc_ensemble_set_batch_large: the batch path on the large kernel
+        on every device's context, so set_batch holds up to 128 x 128"""
+        L.check(L.lib().perc_ensemble_set_batch_large(self.h, int(bool(enable))),
+                "perc_ensemble_set_batch_large")
+        self.large = bool(enable)
         self.batch = L.lib().perc_ensemble_batch(self.h)
 
     def set_workers(self, workers):

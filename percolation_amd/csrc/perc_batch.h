@@ -58,7 +58,7 @@ hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s);
 hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_count, int solve, double Va,
                          double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout);
+                         BatchOut* out, double* iout, bool large = false);
 void dev_batch_free(perc_ctx* h);
 // host side (perc_batch_host.cpp): perc_batch_bondc's two halves, so the
 // ensemble uploads a group's orders once and launches over them many times.
@@ -83,6 +83,51 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
                          double Va, double g0, double leak, int itol, double tol, int itmax,
                          perc_batch_item* out, const int* site_seeds = nullptr,
                          const int* bond_seeds = nullptr);
+// ---- lattices up to 128 x 128 (perc_batch_large.hip: k_batch_cond_large) --
+// One workgroup of 1024 threads, at most kBatchLargeEPT rows per thread: p
+// alone in LDS, every thread's row codes and r in its registers, q held in
+// registers (fast order) or rebuilt from p where r needs it (literal order),
+// x on the 2m electrode-adjacent rows only.  Taken
+// only while perc_set_batch_large is on (perc_ctx::batch_large).
+constexpr int kBatchLargeSites = 16384;  // 128 x 128
+constexpr int kBatchLargeThreads = 1024;
+constexpr int kBatchLargeEPT = 16;  // rows per thread, at most
+// Byte offsets of its LDS arena (every offset a multiple of 16).  Solver
+// view: p (8 N) at 0, x of the first and last m rows (16 m), the literal
+// order's staging row (two sums x 1024 terms).  The labeling view of
+// batch_lds (parent at 0, bocc, member, flags, socc) aliases it and is dead
+// after the barrier that follows the assembly.  The reduction scratch, the
+// form table, the current codes and the counters follow whichever view ends
+// later.
+struct BatchLargeLds {
+  int oX, oStage, oBocc, oMem, oFlag, oSocc, oRed, oOff, oF, oCur, oInt, total;
+};
+BatchLargeLds batch_large_lds(const Geom& g, int kind);
+// host-only check of perc_batch_large_supported
+bool batch_large_supported(const Geom& g, int kind);
+// what dev_batch_run hands the large kernel (k_batch_cond's arguments with
+// this kernel's LDS plan)
+struct BatchLargeArgs {
+  Geom g;
+  int N, nb;
+  const int* bond_first;
+  const StencilForms* forms;
+  const int* rank;
+  const int* rank_s;
+  const int* item_trial;
+  const int* item_count;
+  const int* item_nsites;
+  BatchOut* out;
+  double* iout;
+  int* sflag;
+  int fast, fl, fr, bf_closed;
+  int solve, itol, itmax, cur_rule;
+  double Va, g0, leak, tol;
+  BatchLargeLds L;
+};
+// one launch of k_batch_cond_large<literal, kind> over nitems items on the
+// context's stream (a.L filled here)
+hipError_t dev_batch_large_launch(perc_ctx* h, int kind, bool literal, BatchLargeArgs a, int nitems);
 // ---- threshold scans (perc_batch_scan.hip: k_batch_scan) ----------------
 // sites of the largest lattice one workgroup scans (128 x 128)
 constexpr int kScanSites = 16384;

@@ -553,7 +553,7 @@ hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s) {
 hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_count, int solve, double Va,
                          double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout) {
+                         BatchOut* out, double* iout, bool large) {
   if (nitems == 0) return hipSuccess;
   BatchState* B = batch_state(h);
   hipStream_t st = h->stream;
@@ -625,7 +625,13 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
   a.L = batch_lds(h->g, kind);
   const int nt = batch_threads(h->N);
   hipError_t e;
-  if (nt == 256) e = launch_kind<256>(B, 0, kind, literal, a, nitems, st);
+  if (large) {  // k_batch_cond_large (perc_batch_large.hip): the same arguments, its own LDS plan
+    const BatchLargeArgs b{a.g, a.N, a.nb, a.bond_first, a.forms, a.rank, a.rank_s, a.item_trial,
+                           a.item_count, a.item_nsites, a.out, a.iout, a.sflag, a.fast, a.fl, a.fr,
+                           a.bf_closed, a.solve, a.itol, a.itmax, a.cur_rule, a.Va, a.g0, a.leak, a.tol,
+                           BatchLargeLds{}};
+    e = dev_batch_large_launch(h, kind, literal, b, nitems);
+  } else if (nt == 256) e = launch_kind<256>(B, 0, kind, literal, a, nitems, st);
   else if (nt == 512) e = launch_kind<512>(B, 1, kind, literal, a, nitems, st);
   else e = launch_kind<1024>(B, 2, kind, literal, a, nitems, st);
   HIP_TRY(e);

@@ -1,6 +1,7 @@
 // perc_batch_host.cpp -- host side of the batch path (include/perc.h:
 // perc_batch_supported, perc_batch_bondc, perc_batch_cond_supported,
-// perc_batch_cond, perc_scan_supported, perc_batch_scan and the seeded forms
+// perc_batch_cond, perc_batch_large_supported, perc_set_batch_large,
+// perc_scan_supported, perc_batch_scan and the seeded forms
 // perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded):
 // argument checks, the orders' inverse permutations, the
 // launch geometry and LDS layouts, the fold of the terminal currents and the
@@ -53,15 +54,11 @@ int batch_threads(int N) {
   return nt;
 }
 
-bool batch_supported(const Geom& g, int kind) {
-  if (g.n < 3 || g.m < 3) return false;
-  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
-  const long long N = (long long)(g.n - 2) * g.m;
-  if (N > kBatchRows) return false;
+// every interior row one of the stencil forms, every stencil bond present
+// (k_assemble's sflag bits 1 and 2)
+static bool stencil_rows_ok(const Geom& g) {
   const StencilForms F = stencil_forms(g);
   if (F.nforms <= 0) return false;
-  // every stencil bond present, every interior row one of the forms
-  // (k_assemble's sflag bits 1 and 2)
   for (int s = g.m + 1; s <= g.t - g.m; ++s) {
     int nb[6];
     const int cnt = sorted_neighbours(g, s, nb);
@@ -81,7 +78,51 @@ bool batch_supported(const Geom& g, int kind) {
       if (!bond) return false;
     }
   }
+  return true;
+}
+
+bool batch_supported(const Geom& g, int kind) {
+  if (g.n < 3 || g.m < 3) return false;
+  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  const long long N = (long long)(g.n - 2) * g.m;
+  if (N > kBatchRows) return false;
+  if (!stencil_rows_ok(g)) return false;
   const BatchLds L = batch_lds(g, kind);
+  return L.total + kBatchLdsStatic <= kBatchLdsMax;
+}
+
+BatchLargeLds batch_large_lds(const Geom& g, int kind) {
+  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
+  const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
+  BatchLargeLds L{};
+  L.oX = up16(8 * N);
+  L.oStage = L.oX + up16(16LL * g.m);
+  const int solver_end = L.oStage + 2 * kBatchLargeThreads * (int)sizeof(double);
+  L.oBocc = up16(4 * ((long long)g.t + 1));
+  L.oMem = L.oBocc + up16(nb + 1);
+  L.oFlag = L.oMem + up16(g.t + 1);
+  int label_end = L.oFlag + up16(g.m + 1);
+  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
+    L.oSocc = label_end;
+    label_end = L.oSocc + up16((long long)g.t + 1);
+  }
+  // x and the staging row lie in what the labeling view overhangs of p, or
+  // past it; what the labeling and the assembly read follows both views
+  L.oRed = std::max(solver_end, label_end);
+  L.oOff = L.oRed + up16(48 * sizeof(double));
+  L.oF = L.oOff + up16(kMaxForms * kMaxSlots * sizeof(int));
+  L.oCur = L.oF + up16(sizeof(StencilForms));
+  L.oInt = L.oCur + up16(4LL * g.m);
+  L.total = L.oInt + 64;
+  return L;
+}
+
+bool batch_large_supported(const Geom& g, int kind) {
+  if (g.n < 3 || g.m < 3) return false;
+  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  if ((long long)g.m * g.n > kBatchLargeSites) return false;
+  if (!stencil_rows_ok(g)) return false;
+  const BatchLargeLds L = batch_large_lds(g, kind);
   return L.total + kBatchLdsStatic <= kBatchLdsMax;
 }
 
@@ -187,7 +228,7 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
     const int n = std::min(chunk, nitems - i0);
     e = dev_batch_run(h, kind, cur_rule, n, item_trial + i0, need_s ? item_nsites + i0 : nullptr,
                       need_b ? item_nbonds + i0 : nullptr, solve ? 1 : 0, Va, g0, leak, itol, tol, itmax,
-                      literal, bo.data(), iout.data());
+                      literal, bo.data(), iout.data(), h->batch_large);
     if (e != hipSuccess) return hip_status(e, who);
     for (int i = 0; i < n; ++i) {
       perc_batch_item& it = out[i0 + i];
@@ -306,7 +347,13 @@ int perc_batch_bondc(perc_ctx* h, int ntrials, const int* orders, int nitems, co
     set_error("perc_batch_bondc: itol 1 or 2 only");
     return PERC_EINVAL;
   }
-  if (!batch_supported(h->g)) {
+  if (h->batch_large) {
+    if (!batch_large_supported(h->g, PERC_BOND)) {
+      set_error("perc_batch_bondc: lattice not supported by the large batch kernel "
+                "(perc_batch_large_supported)");
+      return PERC_EINVAL;
+    }
+  } else if (!batch_supported(h->g)) {
     set_error("perc_batch_bondc: lattice not supported by the batch kernel (perc_batch_supported)");
     return PERC_EINVAL;
   }
@@ -329,6 +376,21 @@ int perc_batch_cond_supported(int kind, int lattice, int m, int n, int pbc) {
   if (m < 1 || n < 1 || (long long)m * n >= (1LL << 31) - 16) return 0;
   return batch_supported(make_geom(lattice, m, n, pbc), kind) ? 1 : 0;
 }
+
+int perc_batch_large_supported(int kind, int lattice, int m, int n, int pbc) {
+  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND) return 0;
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n > kBatchLargeSites) return 0;
+  return batch_large_supported(make_geom(lattice, m, n, pbc), kind) ? 1 : 0;
+}
+
+int perc_set_batch_large(perc_ctx* h, int enable) {
+  if (!h) return PERC_EINVAL;
+  h->batch_large = enable != 0;
+  return PERC_OK;
+}
+
+int perc_batch_large(perc_ctx* h) { return h ? (h->batch_large ? 1 : 0) : PERC_EINVAL; }
 
 // perc_batch_cond (seeded = false: site_src / bond_src are order lists) and
 // perc_batch_cond_seeded (true: seed lists, the orders shuffled on the device)
@@ -353,8 +415,13 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
   if (ntrials < 0 || nitems < 0) return bad("ntrials or nitems < 0");
   if (itmax < 0) return bad("itmax < 0");
   if (solve && itol != 1 && itol != 2) return bad("itol 1 or 2 only");
-  if (!batch_supported(h->g, kind))
+  if (h->batch_large) {
+    if (!batch_large_supported(h->g, kind))
+      return bad("lattice not supported by the large batch kernel for this kind "
+                 "(perc_batch_large_supported)");
+  } else if (!batch_supported(h->g, kind)) {
     return bad("lattice not supported by the batch kernel for this kind (perc_batch_cond_supported)");
+  }
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
   if (ntrials && ((need_s && !site_src) || (need_b && !bond_src)))
     return bad(seeded ? "a seed list the kind reads is missing" : "an order list the kind reads is missing");

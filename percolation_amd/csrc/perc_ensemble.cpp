@@ -29,6 +29,7 @@ struct perc_ensemble {
   int ndev = 0;
   int workers = 1;  // contexts (host threads, streams) per device
   int batch = 0;    // perc_ensemble_set_batch: items per launch of the batch path (0: off)
+  bool large = false;  // perc_ensemble_set_batch_large: the batch path on k_batch_cond_large
   int lattice = 0, m = 0, n = 0, pbc = 0;
   std::vector<int> devices;
   std::vector<perc_ctx*> ctx;  // [d * workers + w]
@@ -175,6 +176,7 @@ int perc_ensemble_set_workers(perc_ensemble* e, int workers) {
         std::swap(c, e->ctx[(size_t)d * e->workers + w]);
       } else if (!rc) {
         rc = perc_ctx_create(e->devices[d], e->lattice, e->m, e->n, e->pbc, &c);
+        if (!rc) perc_set_batch_large(c, e->large ? 1 : 0);
       }
     }
   for (perc_ctx* c : e->ctx)  // the contexts beyond the new count
@@ -193,7 +195,8 @@ int perc_ensemble_workers(perc_ensemble* e) { return e ? e->workers : PERC_EINVA
 // Batch path of perc_ensemble_bond_cond: about `items` (trial, grid point)
 // realisations per launch of k_batch_cond, one workgroup each (0, the
 // default: the per-trial loop).  Ignored on a lattice perc_batch_supported
-// refuses: perc_ensemble_batch then returns 0.
+// refuses (perc_batch_large_supported while perc_ensemble_set_batch_large is
+// on): perc_ensemble_batch then returns 0.
 int perc_ensemble_set_batch(perc_ensemble* e, int items) {
   if (!e || items < 0) return PERC_EINVAL;
   e->batch = items;
@@ -202,7 +205,19 @@ int perc_ensemble_set_batch(perc_ensemble* e, int items) {
 
 int perc_ensemble_batch(perc_ensemble* e) {
   if (!e) return PERC_EINVAL;
-  return e->batch > 0 && perc_batch_supported(e->lattice, e->m, e->n, e->pbc) ? e->batch : 0;
+  const int ok = e->large ? perc_batch_large_supported(PERC_BOND, e->lattice, e->m, e->n, e->pbc)
+                          : perc_batch_supported(e->lattice, e->m, e->n, e->pbc);
+  return e->batch > 0 && ok ? e->batch : 0;
+}
+
+// The batch path on k_batch_cond_large (lattices up to 128 x 128): the flag
+// of perc_set_batch_large on every context of every device.
+int perc_ensemble_set_batch_large(perc_ensemble* e, int enable) {
+  if (!e) return PERC_EINVAL;
+  e->large = enable != 0;
+  for (perc_ctx* c : e->ctx)
+    if (c) perc_set_batch_large(c, enable);
+  return PERC_OK;
 }
 
 // stats[d*k .. d*k+k) is device d's vector; on return every slice holds the

@@ -264,6 +264,8 @@ struct perc_ctx {
   perc::KernelTiming timing;
   perc::MarchKnobs knobs;  // as the current dev_solve / dev_bench read them
   void* batch = nullptr;   // perc_batch_bondc's device buffers (perc_batch.hip), made on first use
+  bool batch_large = false;  // perc_set_batch_large: the batch calls run k_batch_cond_large
+  int large_lds[2][3] = {};  // dynamic LDS granted per instantiation of it
   void* scan = nullptr;    // perc_batch_scan's device buffers (perc_batch_scan.hip), made on first use
   void* shuffle = nullptr; // perc_batch_shuffle's device buffers (perc_batch_shuffle.hip), made on first use
 };

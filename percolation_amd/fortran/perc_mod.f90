@@ -291,6 +291,36 @@ module perc_api
       type(c_ptr), value :: e
     end function perc_ensemble_batch
 
+    ! the batch path on the large kernel (lattices up to 128 x 128), set on
+    ! every device's context
+    integer(c_int) function perc_ensemble_set_batch_large(e, enable) &
+        bind(C, name='perc_ensemble_set_batch_large')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: e
+      integer(c_int), value :: enable
+    end function perc_ensemble_set_batch_large
+
+    ! host-only: 1 when the large batch kernel can run this kind on this lattice
+    integer(c_int) function perc_batch_large_supported(kind, lattice, m, n, pbc) &
+        bind(C, name='perc_batch_large_supported')
+      import :: c_int
+      integer(c_int), value :: kind, lattice, m, n, pbc
+    end function perc_batch_large_supported
+
+    ! the context's batch calls on the large kernel (enable /= 0) or the
+    ! default one (0); perc_batch_large reads the flag back
+    integer(c_int) function perc_set_batch_large(h, enable) &
+        bind(C, name='perc_set_batch_large')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+      integer(c_int), value :: enable
+    end function perc_set_batch_large
+
+    integer(c_int) function perc_batch_large(h) bind(C, name='perc_batch_large')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+    end function perc_batch_large
+
     ! host-only: 1 when the batch kernel can run this lattice
     integer(c_int) function perc_batch_supported(lattice, m, n, pbc) &
         bind(C, name='perc_batch_supported')

@@ -531,6 +531,7 @@ int perc_set_dot_order(perc_ctx *h, int order);
 #define PERC_RAN_HOST_FOLD 64 /* PERC_DOT_LITERAL_HOST: the sums folded by the host */
 #define PERC_RAN_XCD_GROUPED 128 /* resident solve: XCD-grouped reductions (else the flat all-gather) */
 /* (bit 256 of out4[1] is retired -- it marked the deferred reductions -- and is not to be reused) */
+#define PERC_RAN_OPEN 512     /* strip-major nibble march: the open-lattice kernels (open-square path alone) */
 int perc_last_solve(perc_ctx *h, int *out4);
 /* err of every iteration of the last solve (linbcg's per-iteration
    `write (*,*) iter, err`, bondc.f:834): min(cap, iterations) values into

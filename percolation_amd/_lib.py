@@ -34,6 +34,7 @@ DOT_FAST, DOT_LITERAL, DOT_LITERAL_HOST = 0, 1, 2
 RAN_OTHER, RAN_MARCH, RAN_SLABS, RAN_RESIDENT, RAN_SMALL = 0, 1, 2, 3, 4
 RAN_LITERAL, RAN_LIT_TERMS, RAN_QFREE, RAN_STRIPS, RAN_NIBBLE, RAN_TAG, RAN_HOST_FOLD = 1, 2, 4, 8, 16, 32, 64
 RAN_XCD_GROUPED = 128
+RAN_OPEN = 512  # (256 is retired: perc.h)
 XPORT_RCCL, XPORT_HOST, XPORT_EXCHANGE = 0, 1, 4
 DSLAB_ID_BYTES = 128
 

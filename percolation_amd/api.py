@@ -367,7 +367,8 @@ class Context:
         """What the last solve actually ran (perc_last_solve): the kernel
         family ('other', 'march', 'slabs', 'resident', 'small'), its flags and
         the iteration count.  lit_terms: the literal folds summed the terms
-        the solve kernels themselves stored (the production kernels ran)."""
+        the solve kernels themselves stored (the production kernels ran).
+        open: the strip-major nibble march ran its open-lattice kernels."""
         out = np.zeros(4, dtype=np.int32)
         L.check(L.lib().perc_last_solve(self.h, out.ctypes.data), "perc_last_solve")
         f = int(out[1])
@@ -376,7 +377,7 @@ class Context:
                     qfree=bool(f & L.RAN_QFREE), strips=bool(f & L.RAN_STRIPS),
                     nibble=bool(f & L.RAN_NIBBLE), tag=bool(f & L.RAN_TAG),
                     host_fold=bool(f & L.RAN_HOST_FOLD), xcd_grouped=bool(f & L.RAN_XCD_GROUPED),
-                    iter=int(out[2]))
+                    open=bool(f & L.RAN_OPEN), iter=int(out[2]))
 
     def matrix_format(self):
         rc = L.lib().perc_matrix_format(self.h)

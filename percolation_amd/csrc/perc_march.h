@@ -548,8 +548,11 @@ struct MState {
 };
 
 // one step: row gr enters the window, then the middle row (gr -+ 1) is
-// finished when it is one of the band's own rows
-template <int MODE, bool UP, bool SM, bool LIT = false, bool PK = false, int ESR = 0>
+// finished when it is one of the band's own rows.
+// OPEN (strip-major nibble codes, open lattice, no slab: select_march): the
+// open-square path alone -- no form test, no map or general path, none of
+// their LDS tables.
+template <int MODE, bool UP, bool SM, bool LIT = false, bool PK = false, int ESR = 0, bool OPEN = false>
 __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, const MBuf& B,
                                            const MRow& R, int gr,
                                            bool first, double bk, double ak,
@@ -587,9 +590,11 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
   if (MODE != kMarchB) {
     // own row; in a slab also the ghost rows, so the next iteration's
     // halo p(k) is at hand (bitwise the neighbour slab's own value)
+    // (OPEN: no slab, and an own row is inside the view)
     const bool own = gr >= g.r0 && gr < g.rend;
-    const bool pst = (unsigned)(gr - B.lo) < (unsigned)(B.hi - B.lo) &&
-                     (own || (a.slab && (gr < 0 || gr >= nrows)));
+    const bool pst = OPEN ? own
+                          : (unsigned)(gr - B.lo) < (unsigned)(B.hi - B.lo) &&
+                                (own || (a.slab && (gr < 0 || gr >= nrows)));
     bst2<kStAux>(B.pn, pst ? melem<SM>(a, B, gr, g.col) * 8u : kOOB, pn);
   }
   MWin Nw;
@@ -624,8 +629,12 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
     const unsigned c0w = W.cM & 0xffffu, c1w = W.cM >> 16;
     const unsigned f0 = c0w >> 11, f1 = c1w >> 11;
     const double2 dM0 = s_dt[diag_idx(c0w)], dM1 = s_dt[diag_idx(c1w)];
-    const unsigned ff = __builtin_amdgcn_readfirstlane(f0);
-    const bool uni = !__any(f0 != ff || f1 != ff) && a.St.F.regular[ff];
+    unsigned ff = 0u;
+    bool uni = false;
+    if constexpr (!OPEN) {
+      ff = __builtin_amdgcn_readfirstlane(f0);
+      uni = !__any(f0 != ff || f1 != ff) && a.St.F.regular[ff];
+    }
     double q0, q1;
     // u16 codes (the row-major march past the Infinity Cache): the same
     // path where the lattice is the open square one (a.sqcls) and every
@@ -637,15 +646,15 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
     // (the row-major nibble march runs on the open square lattice only --
     // the host takes the u16 codes with pbc -- so the other paths are not
     // compiled into it: their registers spilled it at the 4-wave bound)
-    // (PERC_MARCH_PIN_SQ: for counting the open-square walk's instructions
-    // only, tools/march_isa.py -- such a build is wrong under pbc and is
-    // never loaded)
-#if defined(PERC_MARCH_PIN_SQ)
-    if constexpr (PK) sqp = true;
-#else
-    if constexpr (PK && !SM) sqp = true;
-#endif
-    else if constexpr (PK) sqp = !a.T.pbc;
+    // (the strip-major nibble march has one instantiation per boundary:
+    // OPEN with this path alone -- the open lattice, select_march -- and the
+    // other, which runs under pbc only, without it.  That one relies on
+    // march_open: on an open lattice it would still be right -- its rows
+    // carry their column class's bits and take the run-time-mask or map
+    // path -- but slower, and it is never selected there: a slab solve, the
+    // only other reader of !march_open, launches the row-major PQ kernel)
+    if constexpr (OPEN || (PK && !SM)) sqp = true;
+    else if constexpr (PK) sqp = false;
     else if constexpr (SM) sqp = a.sqcls && !__any((((c0w ^ g.cb0) | (c1w ^ g.cb1)) >> 8) != 0u);
     else sqp = false;
     if (sqp) {
@@ -775,7 +784,7 @@ __device__ __forceinline__ void march_step(const CGArgs& a, const MGeom& g, cons
 }
 
 // FT >= 0: `first` is the compile-time constant FT != 0 (march_walk below)
-template <int MODE, int D, bool UP, bool SM, int PAUX, bool PK, bool LIT, int ESR, int FT>
+template <int MODE, int D, bool UP, bool SM, int PAUX, bool PK, bool LIT, int ESR, int FT, bool OPEN>
 __device__ __forceinline__ void march_walk_f(const CGArgs& a, const MGeom& g, const MBuf& B,
                                              MRow (&ring)[D],
                                              bool first_rt, double bk, double ak,
@@ -800,8 +809,8 @@ __device__ __forceinline__ void march_walk_f(const CGArgs& a, const MGeom& g, co
       // view (loads return 0, stores are dropped) and finish no row
       const MRow R = ring[u];
       march_load<MODE, SM, PAUX, PK>(a, g, B, UP ? g.rend - (j + D) : g.r0 - 1 + j + D, first, psrc, ring[u]);
-      march_step<MODE, UP, SM, LIT, PK, ESR>(a, g, B, R, UP ? g.rend - j : g.r0 - 1 + j, first, bk, ak, pnew, s_dt,
-                                            s_rpos, s_rmap, s_w, W, acc, s_ed);
+      march_step<MODE, UP, SM, LIT, PK, ESR, OPEN>(a, g, B, R, UP ? g.rend - j : g.r0 - 1 + j, first, bk, ak, pnew,
+                                                   s_dt, s_rpos, s_rmap, s_w, W, acc, s_ed);
     }
   }
 }
@@ -815,7 +824,8 @@ __device__ __forceinline__ void march_walk_f(const CGArgs& a, const MGeom& g, co
 // every one of 5 rounds (profiles/cmask_ab_L4096.json: `first` vs `main`).
 // PERC_MARCH_FIRST_RT (A/B probe builds only): the run-time `first` in
 // every step, as the u16 kernels keep it.
-template <int MODE, int D, bool UP, bool SM, int PAUX = 0, bool PK = false, bool LIT = false, int ESR = 0>
+template <int MODE, int D, bool UP, bool SM, int PAUX = 0, bool PK = false, bool LIT = false, int ESR = 0,
+          bool OPEN = false>
 __device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, const MBuf& B,
                                            MRow (&ring)[D],
                                            bool first, double bk, double ak,
@@ -830,14 +840,14 @@ __device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, cons
 #endif
   if constexpr (split) {
     if (first)
-      march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, 1>(a, g, B, ring, true, bk, ak, psrc, pnew, s_dt, s_rpos, s_rmap,
-                                                           s_w, acc, s_ed);
+      march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, 1, OPEN>(a, g, B, ring, true, bk, ak, psrc, pnew, s_dt, s_rpos,
+                                                                 s_rmap, s_w, acc, s_ed);
     else
-      march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, 0>(a, g, B, ring, false, bk, ak, psrc, pnew, s_dt, s_rpos, s_rmap,
-                                                           s_w, acc, s_ed);
+      march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, 0, OPEN>(a, g, B, ring, false, bk, ak, psrc, pnew, s_dt, s_rpos,
+                                                                 s_rmap, s_w, acc, s_ed);
   } else {
-    march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, -1>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos, s_rmap,
-                                                          s_w, acc, s_ed);
+    march_walk_f<MODE, D, UP, SM, PAUX, PK, LIT, ESR, -1, OPEN>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos,
+                                                                s_rmap, s_w, acc, s_ed);
   }
 }
 
@@ -853,9 +863,10 @@ __device__ __forceinline__ void march_walk(const CGArgs& a, const MGeom& g, cons
 // when held; the u16 march has 123-126)
 constexpr int march_min_waves(int mode, bool sm, bool pk) { return !sm && pk && mode != kMarchPQ ? 4 : 1; }
 template <int MODE, bool SM = false, int D = kMarchDepth, int PAUX = 0, bool TR = false,
-          bool TAG = false, bool PK = false, bool LIT = false, int ESR = 0>
+          bool TAG = false, bool PK = false, bool LIT = false, int ESR = 0, bool OPEN = false>
 __global__ __launch_bounds__(64 * kMarchWaves, march_min_waves(MODE, SM, PK)) void k_cg_march(CGArgs a) {
   static_assert(ESR == 0 || (MODE == kMarchB && (SM || PK)), "staged edge pairs: the march B with edge pairs");
+  static_assert(!OPEN || (SM && PK && MODE != kMarchPQ), "the open instantiation: the strip-major nibble march");
   const unsigned long long tr_t0 = TR ? wall_clock64() : 0ull;
   unsigned long long tr_t1 = 0ull;
   CGScalars* S = a.S;
@@ -983,9 +994,11 @@ __global__ __launch_bounds__(64 * kMarchWaves, march_min_waves(MODE, SM, PK)) vo
               make_double2(xo[e].x + akp * po[e].x, xo[e].y + akp * po[e].y));
     }
   }
-  if (threadIdx.x < kMaxForms) {
-    s_rpos[threadIdx.x] = a.St.F.rpos[threadIdx.x];
-    s_rmap[threadIdx.x] = a.St.F.rmap[threadIdx.x];
+  if constexpr (!OPEN) {  // (the map / general paths' tables: not in the open instantiation)
+    if (threadIdx.x < kMaxForms) {
+      s_rpos[threadIdx.x] = a.St.F.rpos[threadIdx.x];
+      s_rmap[threadIdx.x] = a.St.F.rmap[threadIdx.x];
+    }
   }
   load_dtab(a.St, s_dt);
   __syncthreads();
@@ -993,17 +1006,17 @@ __global__ __launch_bounds__(64 * kMarchWaves, march_min_waves(MODE, SM, PK)) vo
   const double bknum = S->bknum;  // of this iteration's ak (P's collector epilogue)
   double acc[2] = {0.0, 0.0};
   if (active) {
-    double* s_w = s_win[threadIdx.x >> 6];
+    double* s_w = OPEN ? nullptr : s_win[threadIdx.x >> 6];
     double2* s_ed = nullptr;
     if constexpr (ESR > 0) {
       __shared__ double2 s_edge[kMarchWaves][2 * (ESR > 0 ? ESR : 1)];
       s_ed = s_edge[threadIdx.x >> 6];
     }
     if (up)
-      march_walk<MODE, D, true, SM, PAUX, PK, LIT, ESR>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos,
+      march_walk<MODE, D, true, SM, PAUX, PK, LIT, ESR, OPEN>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos,
                                                        s_rmap, s_w, acc, s_ed);
     else
-      march_walk<MODE, D, false, SM, PAUX, PK, LIT, ESR>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos,
+      march_walk<MODE, D, false, SM, PAUX, PK, LIT, ESR, OPEN>(a, g, B, ring, first, bk, ak, psrc, pnew, s_dt, s_rpos,
                                                         s_rmap, s_w, acc, s_ed);
     if constexpr (ESR > 0) {
       // the band's staged edge pairs: lane l stores row r0 + l of side
@@ -1140,6 +1153,7 @@ struct MarchKey {
   int d, paux;
   bool tr, tag, pk, lit;
   int esr;
+  bool open;  // strip-major nibble codes on an open lattice: the open-square path alone
 };
 using MarchKernel = void (*)(CGArgs);
 struct MarchVariant {
@@ -1158,7 +1172,10 @@ struct MarchVariant {
 // nontemporal last-use loads.  Row-major rows (vectors past the Infinity
 // Cache): kMarchDepth rows, P and B on B's 8-row bands (L = 8192: P 0.314 vs
 // 0.355 ms, r4_8; B's nontemporal r(k) loads 0.300 vs 0.331 ms, r4_3).
-// Columns: MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR (k_cg_march's order).
+// Columns: MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR, OPEN (k_cg_march's
+// order; a row without the last column has OPEN false).  Every strip-major
+// nibble row has an OPEN twin: the twin runs on the open lattice, the row
+// itself under pbc (select_march).
 #define PERC_MARCH_VARIANTS(X) \
   X(PERC_MARCH_PQ)                                                   /* q-storing P+S */ \
   X(kMarchP, true, 3, kNT, false, false, false, false, 0)            /* strip-major P, u16, ticket reduction */ \
@@ -1168,11 +1185,17 @@ struct MarchVariant {
   X(kMarchP, true, 3, kNT, false, false, false, true, 0)             /* strip-major P, u16, literal order */ \
   X(kMarchP, true, 3, kNT, false, true, false, true, 0)              /* strip-major P, u16, literal order, solve tagged */ \
   X(kMarchP, true, 3, kNT, false, false, true, false, 0)             /* strip-major P, nibble, ticket reduction */ \
+  X(kMarchP, true, 3, kNT, false, false, true, false, 0, true)       /* strip-major P, nibble, ticket reduction, open lattice */ \
   X(kMarchP, true, 3, kNT, true, false, true, false, 0)              /* strip-major P, nibble, ticket reduction, phase probe */ \
-  X(kMarchP, true, 3, kNT, false, true, true, false, 0)              /* strip-major P, nibble, tagged granules: the default P */ \
+  X(kMarchP, true, 3, kNT, true, false, true, false, 0, true)        /* strip-major P, nibble, ticket reduction, phase probe, open lattice */ \
+  X(kMarchP, true, 3, kNT, false, true, true, false, 0)              /* strip-major P, nibble, tagged granules (pbc) */ \
+  X(kMarchP, true, 3, kNT, false, true, true, false, 0, true)        /* strip-major P, nibble, tagged granules, open lattice: the default P */ \
   X(kMarchP, true, 3, kNT, true, true, true, false, 0)               /* strip-major P, nibble, tagged granules, phase probe */ \
+  X(kMarchP, true, 3, kNT, true, true, true, false, 0, true)         /* strip-major P, nibble, tagged granules, phase probe, open lattice */ \
   X(kMarchP, true, 3, kNT, false, false, true, true, 0)              /* strip-major P, nibble, literal order */ \
+  X(kMarchP, true, 3, kNT, false, false, true, true, 0, true)        /* strip-major P, nibble, literal order, open lattice */ \
   X(kMarchP, true, 3, kNT, false, true, true, true, 0)               /* strip-major P, nibble, literal order, solve tagged */ \
+  X(kMarchP, true, 3, kNT, false, true, true, true, 0, true)         /* strip-major P, nibble, literal order, solve tagged, open lattice */ \
   X(kMarchB, true, 3, kNT, false, false, false, false, 0)            /* strip-major B, u16, ticket reduction */ \
   X(kMarchB, true, 3, kNT, true, false, false, false, 0)             /* strip-major B, u16, ticket reduction, phase probe */ \
   X(kMarchB, true, 3, kNT, false, true, false, false, 0)             /* strip-major B, u16, tagged granules */ \
@@ -1182,13 +1205,21 @@ struct MarchVariant {
   X(kMarchB, true, 3, kNT, false, true, false, false, kEdgeRows)     /* strip-major B, u16, edge pairs staged in LDS */ \
   X(kMarchB, true, 3, kNT, true, true, false, false, kEdgeRows)      /* strip-major B, u16, staged edge pairs, phase probe */ \
   X(kMarchB, true, 3, kNT, false, false, true, false, 0)             /* strip-major B, nibble, ticket reduction */ \
+  X(kMarchB, true, 3, kNT, false, false, true, false, 0, true)       /* strip-major B, nibble, ticket reduction, open lattice */ \
   X(kMarchB, true, 3, kNT, true, false, true, false, 0)              /* strip-major B, nibble, ticket reduction, phase probe */ \
+  X(kMarchB, true, 3, kNT, true, false, true, false, 0, true)        /* strip-major B, nibble, ticket reduction, phase probe, open lattice */ \
   X(kMarchB, true, 3, kNT, false, true, true, false, 0)              /* strip-major B, nibble, tagged granules */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, 0, true)        /* strip-major B, nibble, tagged granules, open lattice */ \
   X(kMarchB, true, 3, kNT, true, true, true, false, 0)               /* strip-major B, nibble, tagged granules, phase probe */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, 0, true)         /* strip-major B, nibble, tagged granules, phase probe, open lattice */ \
   X(kMarchB, true, 3, kNT, false, false, true, true, 0)              /* strip-major B, nibble, literal order */ \
+  X(kMarchB, true, 3, kNT, false, false, true, true, 0, true)        /* strip-major B, nibble, literal order, open lattice */ \
   X(kMarchB, true, 3, kNT, false, true, true, true, 0)               /* strip-major B, nibble, literal order, solve tagged */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, kEdgeRows)      /* strip-major B, nibble, edge pairs staged in LDS: the default B */ \
+  X(kMarchB, true, 3, kNT, false, true, true, true, 0, true)         /* strip-major B, nibble, literal order, solve tagged, open lattice */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, kEdgeRows)      /* strip-major B, nibble, edge pairs staged in LDS (pbc) */ \
+  X(kMarchB, true, 3, kNT, false, true, true, false, kEdgeRows, true) /* strip-major B, nibble, edge pairs staged in LDS, open lattice: the default B */ \
   X(kMarchB, true, 3, kNT, true, true, true, false, kEdgeRows)       /* strip-major B, nibble, staged edge pairs, phase probe */ \
+  X(kMarchB, true, 3, kNT, true, true, true, false, kEdgeRows, true) /* strip-major B, nibble, staged edge pairs, phase probe, open lattice */ \
   X(kMarchP, false, kMarchDepth, 0, false, false, false, false, 0)   /* row-major P, u16 */ \
   X(kMarchP, false, kMarchDepth, 0, false, false, false, true, 0)    /* row-major P, u16, literal order */ \
   X(kMarchP, false, kMarchDepth, 0, false, false, true, false, 0)    /* row-major P, nibble (128 VGPRs unspilled at the 4-wave bound): past the cache */ \
@@ -1201,7 +1232,7 @@ struct MarchVariant {
 
 constexpr bool operator==(const MarchKey& a, const MarchKey& b) {
   return a.mode == b.mode && a.sm == b.sm && a.d == b.d && a.paux == b.paux && a.tr == b.tr && a.tag == b.tag &&
-         a.pk == b.pk && a.lit == b.lit && a.esr == b.esr;
+         a.pk == b.pk && a.lit == b.lit && a.esr == b.esr && a.open == b.open;
 }
 
 MarchKernel march_pq_kernel() {

@@ -89,17 +89,21 @@ void march_occupancy(const perc_ctx* h, int* cus, int* per_cu) {
 // The march kernel of a launch: mode kMarchP for the P side (P of the q-free
 // march, else the q-storing P+S), kMarchB for the q-free B.
 //  strip-major pair (the default solve at L <= 4096; phase probe: a.mtrace):
-//    staged edges (B, a.mes) > literal > tagged > trace > plain
+//    staged edges (B, a.mes) > literal > tagged > trace > plain; with nibble
+//    codes on an open lattice, outside a slab solve, the OPEN twin of each
+//    (march_open: the open-square path alone; the row itself runs under pbc)
 //  row-major pair (vectors past the Infinity Cache): literal and nibble codes
 //    independently (P's nibble codes: a.rm_pnib), B's staged edges without lit
+bool march_open(const CGArgs& a) { return a.sm && a.nib != nullptr && !a.T.pbc && !a.slab; }
+
 MarchKey select_march(int mode, const perc_ctx* h, const CGArgs& a) {
   if (!h->qfree) return MarchKey{PERC_MARCH_PQ};
   const bool lit = a.lit != nullptr, nib = a.nib != nullptr, tag = a.mgran != nullptr, tr = a.mtrace != nullptr;
   if (!a.sm) {
-    if (mode == kMarchP) return {kMarchP, false, kMarchDepth, 0, false, false, nib && a.rm_pnib, lit, 0};
-    return {kMarchB, false, kMarchDepth, kNT, false, false, nib, lit, !lit && nib && a.mes ? kEdgeRowsRm : 0};
+    if (mode == kMarchP) return {kMarchP, false, kMarchDepth, 0, false, false, nib && a.rm_pnib, lit, 0, false};
+    return {kMarchB, false, kMarchDepth, kNT, false, false, nib, lit, !lit && nib && a.mes ? kEdgeRowsRm : 0, false};
   }
-  const MarchKey k = {mode, true, 3, kNT, false, false, nib, false, 0};
+  const MarchKey k = {mode, true, 3, kNT, false, false, nib, false, 0, march_open(a)};
   auto with = [k](bool tr, bool tag, bool lit, int esr) {
     MarchKey v = k;
     v.tr = tr, v.tag = tag, v.lit = lit, v.esr = esr;
@@ -117,8 +121,8 @@ hipError_t launch_march(perc_ctx* h, int mode, hipStream_t st, const CGArgs& a) 
   const MarchKey k = select_march(mode, h, a);
   const MarchKernel fn = find_march(k);
   if (!fn) {
-    fprintf(stderr, "[perc] march variant {%d, %d, %d, %d, %d, %d, %d, %d, %d} is not compiled\n", k.mode, k.sm, k.d,
-            k.paux, k.tr, k.tag, k.pk, k.lit, k.esr);
+    fprintf(stderr, "[perc] march variant {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d} is not compiled\n", k.mode, k.sm,
+            k.d, k.paux, k.tr, k.tag, k.pk, k.lit, k.esr, k.open);
     return hipErrorInvalidConfiguration;
   }
   klaunch(h, fn, k.sm && a.wslots > 0 ? h->wm_grid : h->march_grid, 64 * kMarchWaves, st, a);
@@ -782,7 +786,7 @@ hipError_t prepare_march(perc_ctx* h, CGArgs& a, int itmax, bool probe) {
   h->last_flags = (h->dot_order != PERC_DOT_FAST ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0) |
                   (h->march && h->qfree ? PERC_RAN_QFREE : 0) | (a.sm ? PERC_RAN_STRIPS : 0) |
                   (a.nib ? PERC_RAN_NIBBLE : 0) | (a.mgran ? PERC_RAN_TAG : 0) |
-                  (host_fold ? PERC_RAN_HOST_FOLD : 0);
+                  (host_fold ? PERC_RAN_HOST_FOLD : 0) | (h->march && h->qfree && march_open(a) ? PERC_RAN_OPEN : 0);
   return hipSuccess;
 }
 }  // namespace

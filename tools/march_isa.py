@@ -18,14 +18,15 @@ Classes go by mnemonic prefix and nothing else.  A loop's count is every
 instruction between its label and its back branch: all paths through the
 body, taken or not, and inner loops' instructions too (inner loops are
 indented).  The walk loops hold D steps (the kernel's third template
-argument): divide by D for one step.  The strip-major
-nibble kernels compile the pbc paths next to the open-square one;
--DPERC_MARCH_PIN_SQ (counting only, never a library to run) compiles the
-open-square path alone, so the walk loop's count is one step's.
+argument): divide by D for one step.  The open-lattice
+instantiations (last template argument true) hold the open-square path
+alone, so a walk loop's count is D steps of it.  The strip-major nibble
+kernels with the last argument false run under pbc and hold the
+run-time-mask, map and general paths.
 
-  python tools/march_isa.py                       # the four default kernels
-  python tools/march_isa.py -D PERC_MARCH_PIN_SQ -D PERC_MARCH_DYNMASK   # the run-time mask (also: PERC_MARCH_FIRST_RT)
-  python tools/march_isa.py --kernel '<1, true, 3, 2, false, true, true, false, 0>'
+  python tools/march_isa.py                       # the default kernels
+  python tools/march_isa.py -D PERC_MARCH_DYNMASK # the run-time mask (also: PERC_MARCH_FIRST_RT)
+  python tools/march_isa.py --kernel '<1, true, 3, 2, false, true, true, false, 0, true>'
   python tools/march_isa.py --asm perc_solve.s    # an assembly file made before
 """
 import argparse
@@ -40,14 +41,16 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "percolation_amd", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
-# k_cg_march<MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR>: the L = 4096
-# pair (strip-major, nibble codes, tagged) and the L = 8192 pair (row-major,
-# nibble codes)
+# k_cg_march<MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR, OPEN>: the L = 4096
+# pair (strip-major, nibble codes, tagged, open lattice), its pbc pair and the
+# L = 8192 pair (row-major, nibble codes)
 DEFAULT = [
-    ("strip-major P", r"k_cg_march<1, true, 3, 2, false, true, true, false, 0>"),
-    ("strip-major B", r"k_cg_march<2, true, 3, 2, false, true, true, false, 64>"),
-    ("row-major nibble P", r"k_cg_march<1, false, 2, 0, false, false, true, false, 0>"),
-    ("row-major nibble B", r"k_cg_march<2, false, 2, 2, false, false, true, false, 16>"),
+    ("strip-major P", r"k_cg_march<1, true, 3, 2, false, true, true, false, 0, true>"),
+    ("strip-major B", r"k_cg_march<2, true, 3, 2, false, true, true, false, 64, true>"),
+    ("strip-major P, pbc", r"k_cg_march<1, true, 3, 2, false, true, true, false, 0, false>"),
+    ("strip-major B, pbc", r"k_cg_march<2, true, 3, 2, false, true, true, false, 64, false>"),
+    ("row-major nibble P", r"k_cg_march<1, false, 2, 0, false, false, true, false, 0, false>"),
+    ("row-major nibble B", r"k_cg_march<2, false, 2, 2, false, false, true, false, 16, false>"),
 ]
 
 CLASSES = ("VALU", "cndmask", "fp64", "SALU", "SMEM", "waits", "LDS", "VMEM")
@@ -168,7 +171,7 @@ def main():
     ap.add_argument("--asm", default=None, help="read this assembly file instead of compiling")
     ap.add_argument("-D", dest="defines", action="append", default=[], help="extra macro of the compile")
     ap.add_argument("--kernel", action="append", default=[],
-                    help="substring of a demangled kernel name (default: the four default march kernels)")
+                    help="substring of a demangled kernel name (default: the default march kernels)")
     ap.add_argument("--keep", default=None, help="also write the assembly to this file")
     ap.add_argument("--min", type=int, default=150, help="skip loops of fewer instructions")
     a = ap.parse_args()

@@ -702,6 +702,71 @@ int perc_set_batch_large(perc_ctx *h, int enable);
 /* the flag: 1 or 0 (PERC_EINVAL for a NULL context) */
 int perc_batch_large(perc_ctx *h);
 
+/* ---- batch conductance with per-bond weights (ConductCalc condtype 2) -- *
+ * The reference's second way to the conductance gives every bond of the
+ * spanning cluster G = -g0 * rand (MATLAB/ConductCalc.m:33-47, 94-97,
+ * 114-118, 136-146).  A disorder average over such conductances is an
+ * ensemble of small lattices, and perc_batch_cond's two kernels cannot run
+ * it: they rebuild every row from a two-value code.  A third one-workgroup
+ * kernel, k_batch_cond_w, keeps the rows' slot values themselves in LDS (one
+ * array of N doubles per slot, beside p; r, q, the diagonal and the form of
+ * a thread's at most 4 rows in its registers; 256 / 512 / 1024 threads) and
+ * multiplies by them in dsprsax's order -- the diagonal, then the used slots
+ * in slot order -- with z = r / d a plain division by the stored diagonal:
+ * the CSR operator perc_conductance runs under perc_set_bond_weights.  Under
+ * PERC_DOT_LITERAL the results are bitwise that single path's, under
+ * PERC_DOT_FAST the workgroup's own fixed tree (the same for an item
+ * wherever it stands in the call).  perc_batch_cond_weighted is
+ * perc_batch_cond with the weights; exactly one of the two inputs is given:
+ *   explicit     weights = nwsets rows of nb doubles, w[id-1] for bond id of
+ *                the bond list; item i uses row item_wset[i].  As
+ *                perc_set_bond_weights(row) before perc_conductance.
+ *   ConductCalc  item i draws rand('twister', item_wseed[i]), one draw per
+ *                bond the rule gives -g0, in bond-list order, 1.0 for the
+ *                others (k_twister_stream generates the draws on the device,
+ *                the kernel places them by an exclusive count over the
+ *                sites).  As perc_set_conductcalc_weights(h, rule,
+ *                item_wseed[i]) after perc_label.
+ * The argument rules, chunking (the weight rows add 8 nb bytes per item to
+ * the 64 MB bound), item records, dot-order handling (PERC_DOT_LITERAL_HOST
+ * runs as literal), solve = 0 and "nitems == 0 is PERC_OK" are
+ * perc_batch_cond's.  The call does not read the perc_set_batch_large flag:
+ * it has its own kernel.  An item several clusters span (fallback = 1) goes
+ * through the single path with its weights set on the context after
+ * perc_label -- perc_set_bond_weights(row) or
+ * perc_set_conductcalc_weights(rule, seed) -- and cleared with
+ * perc_set_bond_weights(h, NULL, 0) after it: a fallback item clears any
+ * weights the caller had set on the context, and leaves the context
+ * unweighted.  PERC_EINVAL (text in perc_last_error), before any device
+ * call: perc_batch_cond's cases; both weight inputs or neither; weights
+ * without item_wset or the reverse; nwsets < 1 in explicit mode; item_wset[i]
+ * outside 0..nwsets-1; a lattice perc_batch_weighted_supported refuses (the
+ * text names it). */
+/* host-only: 1 when the weighted batch kernel can run this kind on this
+   lattice: m, n >= 3, even m on the triangular lattice, at most 4096 interior
+   rows (4 per thread), every interior row a stencil form with every stencil
+   bond present, and the kernel's LDS arena (p, the slot values, the electrode
+   rows' values) within a workgroup's 160 KB: every square and triangular
+   lattice of 10 x 10 .. 50 x 50, open or periodic.  Accepts no lattice
+   perc_batch_large_supported refuses. */
+int perc_batch_weighted_supported(int kind, int lattice, int m, int n, int pbc);
+int perc_batch_cond_weighted(perc_ctx *h, int kind, int rule, int cur_rule, int ntrials,
+                             const int *site_orders /* ntrials x (t+1), NULL for PERC_BOND */,
+                             const int *bond_orders /* ntrials x (nb+1), NULL for PERC_SITE */,
+                             int nitems, const int *item_trial,
+                             const int *item_nsites /* NULL for PERC_BOND */,
+                             const int *item_nbonds /* NULL for PERC_SITE */,
+                             int nwsets, const double *weights /* nwsets x nb, or NULL */,
+                             const int *item_wset /* nitems, with weights */,
+                             const unsigned int *item_wseed /* nitems, or NULL */,
+                             int solve, double Va, double g0, double leak, int itol,
+                             double tol, int itmax, perc_batch_item *out);
+/* the device generator on its own: n genrand_res53 doubles per seed, bit for
+   bit perc_twister_uniform(seed, n); out = nseeds rows of n (host).
+   PERC_EINVAL: n < 0 or nseeds < 0. */
+int perc_batch_twister(perc_ctx *h, int nseeds, const unsigned int *seeds, long long n,
+                       double *out);
+
 /* ---- batch of small threshold scans (one workgroup each) -------------- *
  * The reference's threshold programs (Fortran/Square/bond_perc.f:204-366,
  * site_perc.f:150-256, sb_perc.f:104-372, bs_perc.f:104-395) are ensembles

@@ -189,6 +189,11 @@ SIGNATURES = {
     "perc_batch_cond": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP,
                                   _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                   C.c_double, C.c_int, _VP]),
+    "perc_batch_weighted_supported": (C.c_int, [C.c_int] * 5),
+    "perc_batch_cond_weighted": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP,
+                                           _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_double,
+                                           C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _VP]),
+    "perc_batch_twister": (C.c_int, [_VP, C.c_int, _VP, C.c_longlong, _VP]),
     "perc_batch_large_supported": (C.c_int, [C.c_int] * 5),
     "perc_set_batch_large": (C.c_int, [_VP, C.c_int]),
     "perc_batch_large": (C.c_int, [_VP]),

@@ -117,6 +117,15 @@ def batch_large_supported(kind, lattice, m, n, pbc=0):
     return bool(L.lib().perc_batch_large_supported(int(kind), lattice, m, n, pbc))
 
 
+def batch_weighted_supported(kind, lattice, m, n, pbc=0):
+    """perc_batch_weighted_supported (host-only): True when the weighted batch
+    kernel (Context.batch_cond with weights / item_wseed) can run this kind on
+    this lattice -- m, n >= 3, at most 4096 interior rows, stencil operator,
+    the slot values of every row within the workgroup's LDS; every lattice of
+    10 x 10 .. 50 x 50."""
+    return bool(L.lib().perc_batch_weighted_supported(int(kind), lattice, m, n, pbc))
+
+
 KIND_RULE = {L.BOND: L.RULE_BOND, L.SITE: L.RULE_SITE, L.SITEBOND: L.RULE_MIXED}
 
 
@@ -437,7 +446,8 @@ class Context:
 
     def batch_cond(self, kind, item_trial, site_orders=None, bond_orders=None, item_nsites=None,
                    item_nbonds=None, rule=None, cur_rule=None, solve=True, Va=1.0, g0=1.0, leak=LEAK,
-                   itol=2, tol=1e-8, itmax=2500, site_seeds=None, bond_seeds=None):
+                   itol=2, tol=1e-8, itmax=2500, site_seeds=None, bond_seeds=None, weights=None,
+                   item_wset=None, item_wseed=None):
         """perc_batch_cond: many small bond, site or mixed realisations in one
         launch, one workgroup each.  kind BOND: bond_orders (ntrials, nb + 1)
         and item_nbonds; SITE: site_orders (ntrials, t + 1) and item_nsites;
@@ -449,7 +459,12 @@ class Context:
         solve=False stops after the spanning test.  The dot order is the
         context's.  site_seeds / bond_seeds (one seed per trial) in place of
         the order lists: perc_batch_cond_seeded, the orders shuffled on the
-        device -- the same items."""
+        device -- the same items.  With any of weights / item_wset / item_wseed
+        given: perc_batch_cond_weighted (ConductCalc.m condtype 2), the kernel
+        that keeps the rows' values -- weights (nwsets, nb) per-bond multipliers
+        with item_wset[i] the row item i uses (set_bond_weights(row) per item),
+        or item_wseed[i] the rand('twister') seed item i draws with
+        (set_conductcalc_weights(rule, seed) per item); order lists only."""
         kind = int(kind)
         if rule is None:
             rule = KIND_RULE.get(kind, -1)  # (an unknown kind: libperc reports it)
@@ -488,12 +503,42 @@ class Context:
             if c is not None and c.shape != it.shape:
                 raise ValueError("item_trial and the count lists differ in length")
         out = (L.BatchItem * max(len(it), 1))()
+        if weights is not None or item_wset is not None or item_wseed is not None:
+            if seeded:
+                raise ValueError("weights go with order lists, not seeds")
+            w = ws = wd = None
+            if weights is not None:
+                w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, self.nb)
+            if item_wset is not None:
+                ws = np.ascontiguousarray(item_wset, dtype=np.int32).reshape(-1)
+            if item_wseed is not None:
+                wd = np.ascontiguousarray(np.asarray(item_wseed, dtype=np.int64) & 0xFFFFFFFF,
+                                          dtype=np.uint32).reshape(-1)
+            for c in (ws, wd):
+                if c is not None and c.shape != it.shape:
+                    raise ValueError("item_trial and item_wset / item_wseed differ in length")
+            L.check(L.lib().perc_batch_cond_weighted(
+                self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so), L.ptr(bo), len(it), L.ptr(it),
+                L.ptr(ns), L.ptr(nbc), 0 if w is None else w.shape[0], L.ptr(w), L.ptr(ws), L.ptr(wd),
+                1 if solve else 0, Va, g0, leak, itol, tol, itmax, C.cast(out, C.c_void_p)),
+                "perc_batch_cond_weighted")
+            return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
         name = "perc_batch_cond_seeded" if seeded else "perc_batch_cond"
         L.check(getattr(L.lib(), name)(self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so),
                                        L.ptr(bo), len(it), L.ptr(it), L.ptr(ns), L.ptr(nbc),
                                        1 if solve else 0, Va, g0, leak, itol, tol, itmax,
                                        C.cast(out, C.c_void_p)), name)
         return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
+
+    def batch_twister(self, seeds, n):
+        """perc_batch_twister: n draws of rand('twister', seed) per seed on the
+        device (k_twister_stream, one wave per seed), bit for bit
+        twister_uniform(seed, n).  Returns (len(seeds), n) doubles."""
+        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32).reshape(-1)
+        n = int(n)
+        out = np.zeros((len(sd), max(n, 0)))
+        L.check(L.lib().perc_batch_twister(self.h, len(sd), L.ptr(sd), n, L.ptr(out)), "perc_batch_twister")
+        return out
 
     def batch_scan(self, kind, site_orders=None, bond_orders=None, scan=L.BOND, fixed=None):
         """perc_batch_scan: many small threshold-scan trials in one launch,
@@ -956,7 +1001,7 @@ def bond_cond_grid(lattice=0, m=10, n=10, pbc=0, master=58302, numtrials=1, Va=1
 
 def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0.9, 1.0), master=58302,
                numtrials=1, batch=256, cur_rule=None, Va=1.0, g0=1.0, tol=1e-8, itmax=2500, ctx=None,
-               device=0, device_shuffle=False, large=False):
+               device=0, device_shuffle=False, large=False, condtype=1, wseed=1838534):
     """The mean conductance curve of site or mixed percolation over trials:
     G(ps) (kind SITE, site.f + ConductCalc.m's site rule; grid a list of ps) or
     G(ps, pb) (kind SITEBOND, sitebond.f + the mixed rule; grid a list of
@@ -974,6 +1019,12 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
     large=True: the context's set_batch_large flag set for the call (restored
     after it) and batch_large_supported in place of batch_cond_supported, so
     the batch path runs up to 128 x 128.
+    condtype=2 (ConductCalc.m's random conductances): item (trial index ii,
+    point j) draws its bond weights with seed (wseed + ii * npts + j) mod 2^32
+    -- batched (where batch_weighted_supported accepts the lattice) through
+    batch_cond's item_wseed, else set_conductcalc_weights after label() and
+    set_bond_weights(None) after the solve; the orders come from the host
+    (device_shuffle is ignored), large=True is a ValueError.
     cur_rule=None: CUR_MATLAB, the
     reference's pairing.  The dot order is the context's (ctx).  Returns
     (trials, stats): per trial dict(ii, seed | sseed, bseed, rows) with one row
@@ -986,6 +1037,10 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
         raise ValueError("cond_curve: kind SITE or SITEBOND (bond: Ensemble.bond_cond)")
     if numtrials < 0:
         raise ValueError("numtrials < 0")
+    if condtype not in (1, 2):
+        raise ValueError("cond_curve: condtype 1 or 2")
+    if condtype == 2 and large:
+        raise ValueError("cond_curve: condtype 2 has its own batch kernel (no large=True)")
     mixed = kind == L.SITEBOND
     rule = KIND_RULE[kind]
     if cur_rule is None:
@@ -1006,9 +1061,11 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
         else:
             ss, bs = trial_seeds(master, max(numtrials, 1)), None
         supported = batch_large_supported if ctx.batch_large() else batch_cond_supported
+        if condtype == 2:
+            supported = batch_weighted_supported
         batched = batch > 0 and npts > 0 and supported(kind, ctx.lattice, ctx.m, ctx.n, ctx.pbc)
         group = max(1, batch // max(npts, 1)) if batched else 1
-        seeded = batched and device_shuffle and _device_shuffle_ok(ctx, kind)
+        seeded = batched and device_shuffle and condtype == 1 and _device_shuffle_ok(ctx, kind)
         stats = np.zeros(npts * 5)
         acc = L.lib().perc_stats_accumulate
         out = []
@@ -1023,6 +1080,8 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
                 src = dict(site_orders=so, bond_orders=bo)
             if batched:
                 it = np.repeat(np.arange(len(tr), dtype=np.int32), npts)
+                if condtype == 2:
+                    src["item_wseed"] = [(wseed + ii * npts + j) & 0xFFFFFFFF for ii in tr for j in range(npts)]
                 res = ctx.batch_cond(kind, it, **src,
                                      item_nsites=np.tile(cnt_s, len(tr)),
                                      item_nbonds=np.tile(cnt_b, len(tr)) if mixed else None,
@@ -1038,7 +1097,11 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
                         else:
                             ctx.occupy(kind, site_order=so[k], nsites=int(cnt_s[j]))
                         li = ctx.label()
+                        if condtype == 2:
+                            ctx.set_conductcalc_weights(rule, (wseed + tr[k] * npts + j) & 0xFFFFFFFF)
                         c = ctx.conductance(rule, cur_rule, Va, g0, LEAK, 2, tol, itmax)
+                        if condtype == 2:
+                            ctx.set_bond_weights(None)
                         res.append(dict(gtop=c["gtop"], gbot=c["gbot"], iter=c["iter"], nspan=li["nspan"]))
             for k, ii in enumerate(tr):
                 rows = []

@@ -31,14 +31,19 @@ __device__ __forceinline__ double bond_value(int rule, int id, int s, int c, int
 // consumer asks for it (ensure_csr): 2 + 8 B per row instead of 50.
 // assemble_row_vals: the row's code and rhs returned through *code_out /
 // *rhs_out (the batch kernel keeps them in LDS and registers);
-// assemble_row stores them at code[i] / rhs[i].
+// assemble_row stores them at code[i] / rhs[i].  gvs_out (optional): the
+// row's slot values gvs_out[j * gvs_stride], j < cnt, in slot order, 0.0 for
+// a slot without its bond (the weighted batch kernel's per-slot arrays in
+// LDS; a null pointer, the default, leaves every other instantiation as it
+// was).
 template <bool CSR>
 __device__ __forceinline__ void assemble_row_vals(
     const Geom& g, int i, const int* bond_first, const uint8_t* bocc, const uint8_t* socc,
     const int* parent, const int* rowptr, double* val, double* diag, double* rhs_out,
     uint16_t* code_out, int* sflag, const StencilForms& F, int fast_form, int fast_l, int fast_r, int bf_closed,
     int rule, double g0,
-    double leak, double Va, int span_root, const double* w) {
+    double leak, double Va, int span_root, const double* w, double* gvs_out = nullptr,
+    int gvs_stride = 1) {
   const int m = g.m, t = g.t, s = i + m + 1;
   const int ps = parent[s];
   const int sr = div_m(g, s - 1), sc = s - 1 - sr * m;
@@ -111,6 +116,7 @@ __device__ __forceinline__ void assemble_row_vals(
       if (gv == -g0) bits |= 1u << j;
       rowsum = rowsum + gv;
       if (CSR && cs[j] > m && cs[j] <= t - m) val[k++] = gv;
+      if (gvs_out) gvs_out[j * gvs_stride] = gv;
     }
     *code_out = (uint16_t)(bits | (unsigned)cnt << 8 | (unsigned)cform << 11);
     if (CSR) diag[i] = -rowsum;
@@ -155,9 +161,11 @@ __device__ __forceinline__ void assemble_row_vals(
     }
     if (id < 0) {  // no bond in this slot: the stencil operator cannot be used
       atomicOr(sflag, 1);
+      if (gvs_out) gvs_out[j * gvs_stride] = 0.0;
       continue;
     }
     const double gv = bond_value(rule, id, s, c, ps, bocc, socc, span_root, g0, leak, w);
+    if (gvs_out) gvs_out[j * gvs_stride] = gv;
     if (gv == -g0) bits |= 1u << j;
     rowsum = rowsum + gv;
     if (CSR && c > m && c <= t - m) val[k++] = gv;

@@ -52,13 +52,16 @@ bool batch_supported(const Geom& g, int kind = PERC_BOND);
 // site ranks (rank_s[tr * t + s - 1]) go beside them for the site and mixed
 // kinds; dev_batch_run reads the arrays its kind needs (item_nsites /
 // item_count may be NULL where the kind does not read them) and refuses an
-// item whose trial lies outside them.
+// item whose trial lies outside them.  wts (optional): the items' per-bond
+// weights -- the launch is k_batch_cond_w's, whatever `large` says.
+struct BatchWeights;
 hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank);
 hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s);
 hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_count, int solve, double Va,
                          double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout, bool large = false);
+                         BatchOut* out, double* iout, bool large = false,
+                         const BatchWeights* wts = nullptr);
 void dev_batch_free(perc_ctx* h);
 // host side (perc_batch_host.cpp): perc_batch_bondc's two halves, so the
 // ensemble uploads a group's orders once and launches over them many times.
@@ -76,13 +79,15 @@ int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_
 int batch_upload_site_orders(perc_ctx* h, int ntrials, const int* site_orders);
 // A NULL order list the kind reads stands for its seeds (perc_batch_cond_seeded:
 // the ranks came from dev_shuffle_run): the replay regenerates that trial's
-// order with perc_shuffle_seeded.
+// order with perc_shuffle_seeded.  wts (optional): the call's per-bond weights
+// (perc_batch_cond_weighted) -- k_batch_cond_w's launches, and a replayed
+// item's weights set on the context after its labeling and cleared after it.
 int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_orders,
                          const int* bond_orders, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_nbonds, int solve, bool replay,
                          double Va, double g0, double leak, int itol, double tol, int itmax,
                          perc_batch_item* out, const int* site_seeds = nullptr,
-                         const int* bond_seeds = nullptr);
+                         const int* bond_seeds = nullptr, const BatchWeights* wts = nullptr);
 // ---- lattices up to 128 x 128 (perc_batch_large.hip: k_batch_cond_large) --
 // One workgroup of 1024 threads, at most kBatchLargeEPT rows per thread: p
 // alone in LDS, every thread's row codes and r in its registers, q held in
@@ -128,6 +133,75 @@ struct BatchLargeArgs {
 // one launch of k_batch_cond_large<literal, kind> over nitems items on the
 // context's stream (a.L filled here)
 hipError_t dev_batch_large_launch(perc_ctx* h, int kind, bool literal, BatchLargeArgs a, int nitems);
+// ---- per-bond weights (perc_batch_weighted.hip: k_batch_cond_w) ---------
+// k_batch_cond_large's scheme (p alone of the N-sized solver arrays in LDS,
+// r, the diagonal, q and the form / count of a thread's own rows in its
+// registers, x on the 2m electrode-adjacent rows) with the rows' slot values
+// themselves in LDS, one array of N doubles per slot, where the other two
+// kernels rebuild them from a two-value code.  256 / 512 / 1024 threads, at
+// most kBatchWEPT rows per thread.
+constexpr int kBatchWEPT = 4;
+constexpr int kBatchWRows = 1024 * kBatchWEPT;
+// threads per workgroup: the fewest of 256 / 512 / 1024 that keep kBatchWEPT
+// rows per thread
+int batch_w_threads(int N);
+// Byte offsets of its LDS arena (every offset a multiple of 16).  Solver
+// view: p (8 N) at 0, x of the first and last m rows (16 m), the literal
+// order's staging row (two sums x NT terms).  The labeling view of batch_lds
+// aliases it.  After whichever view ends later, outside both: the slot values
+// (scn arrays of 8 N bytes; the assembly writes them while it still reads
+// parent and bocc), the electrode rows' slot values (2m sites x 6 doubles),
+// the reduction scratch, the form table and 32 counters.
+struct BatchWLds {
+  int oX, oStage, oBocc, oMem, oFlag, oSocc, oVal, oEl, oRed, oOff, oF, oInt, total;
+};
+BatchWLds batch_w_lds(const Geom& g, int kind);
+// host-only check of perc_batch_weighted_supported
+bool batch_w_supported(const Geom& g, int kind);
+// The weights of one perc_batch_cond_weighted call (host arrays, the items'
+// entries at the chunk's offset): explicit rows (weights: nwsets x nb,
+// item_wset) or ConductCalc seeds (item_wseed), never both.
+struct BatchWeights {
+  int nwsets = 0;
+  const double* weights = nullptr;
+  const int* item_wset = nullptr;
+  const unsigned* item_wseed = nullptr;
+};
+// what dev_batch_run hands the weighted kernel: k_batch_cond_large's
+// arguments, and per item either its weight row (wrows + item_wset[i] * nb)
+// or its draws (u + i * nb, from k_twister_stream) and its row of the
+// launch's scratch (wscratch + i * wstride; wstride = nb rounded up to 16
+// doubles, so that no two workgroups write one 128-byte line)
+struct BatchWArgs {
+  Geom g;
+  int N, nb;
+  const int* bond_first;
+  const StencilForms* forms;
+  const int* rank;
+  const int* rank_s;
+  const int* item_trial;
+  const int* item_count;
+  const int* item_nsites;
+  const int* item_wset;   // explicit mode, else NULL
+  const double* wrows;
+  const double* u;        // ConductCalc mode
+  double* wscratch;
+  int wstride;
+  BatchOut* out;
+  double* iout;
+  int* sflag;
+  int fast, fl, fr, bf_closed;
+  int solve, itol, itmax, cur_rule;
+  double Va, g0, leak, tol;
+  BatchWLds L;
+};
+// one launch of k_batch_cond_w<threads, literal, kind> over nitems items on
+// the context's stream (a.L filled here)
+hipError_t dev_batch_w_launch(perc_ctx* h, int kind, bool literal, BatchWArgs a, int nitems);
+// k_twister_stream: n genrand_res53 doubles per seed (d_seeds, d_out: device)
+hipError_t dev_twister_launch(perc_ctx* h, int nseeds, const unsigned* d_seeds, long long n, double* d_out);
+// perc_batch_twister: seeds and out on the host, through the batch buffers
+hipError_t dev_batch_twister(perc_ctx* h, int nseeds, const unsigned* seeds, long long n, double* out);
 // ---- threshold scans (perc_batch_scan.hip: k_batch_scan) ----------------
 // sites of the largest lattice one workgroup scans (128 x 128)
 constexpr int kScanSites = 16384;

@@ -443,7 +443,27 @@ struct BatchState {
   size_t item_cap = 0, iout_cap = 0;
   int* d_sflag = nullptr;
   int lds_attr[3][2][3] = {};  // dynamic LDS granted per instantiation
+  // perc_batch_cond_weighted: the chunk's explicit weight rows or its draws
+  // (d_wsrc), the ConductCalc rows the kernel writes (d_wscr, items x nb), the
+  // items' row numbers or seeds (d_wsel); perc_batch_twister's seeds and
+  // output go through d_wsel and d_wsrc too
+  double* d_wsrc = nullptr;
+  double* d_wscr = nullptr;
+  unsigned* d_wsel = nullptr;
+  size_t wsrc_cap = 0, wscr_cap = 0, wsel_cap = 0;
 };
+
+// *p grown to n elements (capacity *cap); the contents are not kept
+template <class T>
+hipError_t grow(T** p, size_t* cap, size_t n) {
+  if (*cap >= n) return hipSuccess;
+  if (*p) HIP_TRY(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(dmalloc(p, n));
+  *cap = n;
+  return hipSuccess;
+}
 
 template <int NT, bool LIT, int KIND>
 hipError_t launch(BatchState* B, int slot, const BatchArgs& a, int nitems, hipStream_t st) {
@@ -498,6 +518,9 @@ void dev_batch_free(perc_ctx* h) {
   (void)hipFree(B->d_out);
   (void)hipFree(B->d_iout);
   (void)hipFree(B->d_sflag);
+  (void)hipFree(B->d_wsrc);
+  (void)hipFree(B->d_wscr);
+  (void)hipFree(B->d_wsel);
   delete B;
   h->batch = nullptr;
 }
@@ -550,10 +573,29 @@ hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s) {
   return hipSuccess;
 }
 
+hipError_t dev_batch_twister(perc_ctx* h, int nseeds, const unsigned* seeds, long long n, double* out) {
+  if (nseeds <= 0 || n <= 0) return hipSuccess;
+  BatchState* B = batch_state(h);
+  hipStream_t st = h->stream;
+  // launches whose output stays under 64 MB of device memory
+  const long long per = std::max(1LL, std::min<long long>(nseeds, (64LL << 20) / (8 * n)));
+  HIP_TRY(grow(&B->d_wsel, &B->wsel_cap, (size_t)per));
+  HIP_TRY(grow(&B->d_wsrc, &B->wsrc_cap, (size_t)per * (size_t)n));
+  for (long long s0 = 0; s0 < nseeds; s0 += per) {
+    const int k = (int)std::min<long long>(per, nseeds - s0);
+    HIP_TRY(hipMemcpyAsync(B->d_wsel, seeds + s0, sizeof(unsigned) * k, hipMemcpyHostToDevice, st));
+    HIP_TRY(dev_twister_launch(h, k, B->d_wsel, n, B->d_wsrc));
+    HIP_TRY(hipMemcpyAsync(out + (size_t)s0 * (size_t)n, B->d_wsrc, sizeof(double) * (size_t)k * (size_t)n,
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return hipSuccess;
+}
+
 hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_count, int solve, double Va,
                          double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout, bool large) {
+                         BatchOut* out, double* iout, bool large, const BatchWeights* wts) {
   if (nitems == 0) return hipSuccess;
   BatchState* B = batch_state(h);
   hipStream_t st = h->stream;
@@ -625,7 +667,43 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
   a.L = batch_lds(h->g, kind);
   const int nt = batch_threads(h->N);
   hipError_t e;
-  if (large) {  // k_batch_cond_large (perc_batch_large.hip): the same arguments, its own LDS plan
+  if (wts) {  // k_batch_cond_w (perc_batch_weighted.hip): the same arguments, its own LDS plan, the weights
+    const size_t nb = (size_t)a.nb;
+    BatchWArgs b{a.g, a.N, a.nb, a.bond_first, a.forms, a.rank, a.rank_s, a.item_trial, a.item_count,
+                 a.item_nsites, nullptr, nullptr, nullptr, nullptr, 0, a.out, a.iout, a.sflag, a.fast, a.fl,
+                 a.fr, a.bf_closed, a.solve, a.itol, a.itmax, a.cur_rule, a.Va, a.g0, a.leak, a.tol,
+                 BatchWLds{}};
+    HIP_TRY(grow(&B->d_wsel, &B->wsel_cap, (size_t)nitems));
+    if (wts->item_wset) {
+      // the rows this launch's items name, each uploaded once, numbered as met
+      std::vector<int> local((size_t)wts->nwsets, -1), sel((size_t)nitems), rows;
+      for (int i = 0; i < nitems; ++i) {
+        int& l = local[(size_t)wts->item_wset[i]];
+        if (l < 0) {
+          l = (int)rows.size();
+          rows.push_back(wts->item_wset[i]);
+        }
+        sel[i] = l;
+      }
+      HIP_TRY(grow(&B->d_wsrc, &B->wsrc_cap, rows.size() * nb));
+      for (size_t r = 0; r < rows.size(); ++r)
+        HIP_TRY(hipMemcpyAsync(B->d_wsrc + r * nb, wts->weights + (size_t)rows[r] * nb, sizeof(double) * nb,
+                               hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(B->d_wsel, sel.data(), sizeof(int) * nitems, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));  // (sel goes away)
+      b.item_wset = reinterpret_cast<const int*>(B->d_wsel);
+      b.wrows = B->d_wsrc;
+    } else {
+      HIP_TRY(grow(&B->d_wsrc, &B->wsrc_cap, (size_t)nitems * nb));
+      b.wstride = (a.nb + 15) & ~15;
+      HIP_TRY(grow(&B->d_wscr, &B->wscr_cap, (size_t)nitems * (size_t)b.wstride));
+      HIP_TRY(hipMemcpyAsync(B->d_wsel, wts->item_wseed, sizeof(unsigned) * nitems, hipMemcpyHostToDevice, st));
+      HIP_TRY(dev_twister_launch(h, nitems, B->d_wsel, (long long)nb, B->d_wsrc));
+      b.u = B->d_wsrc;
+      b.wscratch = B->d_wscr;
+    }
+    e = dev_batch_w_launch(h, kind, literal, b, nitems);
+  } else if (large) {  // k_batch_cond_large (perc_batch_large.hip): the same arguments, its own LDS plan
     const BatchLargeArgs b{a.g, a.N, a.nb, a.bond_first, a.forms, a.rank, a.rank_s, a.item_trial,
                            a.item_count, a.item_nsites, a.out, a.iout, a.sflag, a.fast, a.fl, a.fr,
                            a.bf_closed, a.solve, a.itol, a.itmax, a.cur_rule, a.Va, a.g0, a.leak, a.tol,

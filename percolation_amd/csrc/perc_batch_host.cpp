@@ -2,7 +2,9 @@
 // perc_batch_supported, perc_batch_bondc, perc_batch_cond_supported,
 // perc_batch_cond, perc_batch_large_supported, perc_set_batch_large,
 // perc_scan_supported, perc_batch_scan and the seeded forms
-// perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded):
+// perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded, and the
+// weighted perc_batch_weighted_supported, perc_batch_cond_weighted,
+// perc_batch_twister):
 // argument checks, the orders' inverse permutations, the
 // launch geometry and LDS layouts, the fold of the terminal currents and the
 // single-path replay of the items several clusters span.
@@ -126,6 +128,46 @@ bool batch_large_supported(const Geom& g, int kind) {
   return L.total + kBatchLdsStatic <= kBatchLdsMax;
 }
 
+int batch_w_threads(int N) { return N <= 256 * kBatchWEPT ? 256 : (N <= 512 * kBatchWEPT ? 512 : 1024); }
+
+BatchWLds batch_w_lds(const Geom& g, int kind) {
+  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
+  const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
+  const int nt = batch_w_threads((int)std::min<long long>(N, kBatchWRows));
+  BatchWLds L{};
+  L.oX = up16(8 * N);
+  L.oStage = L.oX + up16(16LL * g.m);
+  const int solver_end = L.oStage + 2 * nt * (int)sizeof(double);
+  L.oBocc = up16(4 * ((long long)g.t + 1));
+  L.oMem = L.oBocc + up16(nb + 1);
+  L.oFlag = L.oMem + up16(g.t + 1);
+  int label_end = L.oFlag + up16(g.m + 1);
+  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
+    L.oSocc = label_end;
+    label_end = L.oSocc + up16((long long)g.t + 1);
+  }
+  // the slot values are written while the labeling view is still read and
+  // read while the solver view is live: past both
+  L.oVal = std::max(solver_end, label_end);
+  L.oEl = L.oVal + up16(8LL * g.scn * N);
+  L.oRed = L.oEl + up16(8LL * 6 * 2 * g.m);
+  L.oOff = L.oRed + up16(48 * sizeof(double));
+  L.oF = L.oOff + up16(kMaxForms * kMaxSlots * sizeof(int));
+  L.oInt = L.oF + up16(sizeof(StencilForms));
+  L.total = L.oInt + 128;
+  return L;
+}
+
+bool batch_w_supported(const Geom& g, int kind) {
+  if (g.n < 3 || g.m < 3) return false;
+  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  const long long N = (long long)(g.n - 2) * g.m;
+  if (N > kBatchWRows) return false;  // kBatchWEPT rows per thread at 1024 threads
+  if (!batch_large_supported(g, kind)) return false;  // (its checks, stencil_rows_ok among them)
+  const BatchWLds L = batch_w_lds(g, kind);
+  return (long long)L.total + kBatchLdsStatic <= kBatchLdsMax;
+}
+
 ScanLds scan_lds(const Geom& g) {
   auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
   ScanLds L{};
@@ -211,7 +253,8 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
                          const int* bond_orders, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_nbonds, int solve, bool replay,
                          double Va, double g0, double leak, int itol, double tol, int itmax,
-                         perc_batch_item* out, const int* site_seeds, const int* bond_seeds) {
+                         perc_batch_item* out, const int* site_seeds, const int* bond_seeds,
+                         const BatchWeights* wts) {
   const int nb = (int)h->nb, m = h->g.m, t = h->g.t;
   const int rule = kind;  // (PERC_RULE_* of a kind has the kind's number)
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
@@ -220,15 +263,23 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
   hipError_t e;
   const bool literal = h->dot_order != PERC_DOT_FAST;
   // launches of bounded size (the iout rows: 16 m bytes per item)
-  const int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
+  int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
+  // ... and the weighted kernel's rows (its draws, its scratch: 8 nb bytes per item each)
+  if (wts) chunk = std::max(1, std::min(chunk, (int)((64LL << 20) / (8LL * (nb + 16)))));
   std::vector<BatchOut> bo((size_t)std::min(nitems, chunk));
   std::vector<double> iout(solve ? bo.size() * 2 * (size_t)m : 0);
   std::vector<int> slist, blist, sregen, bregen;
   for (int i0 = 0; i0 < nitems; i0 += chunk) {
     const int n = std::min(chunk, nitems - i0);
+    BatchWeights wc;
+    if (wts) {
+      wc = *wts;
+      if (wc.item_wset) wc.item_wset += i0;
+      if (wc.item_wseed) wc.item_wseed += i0;
+    }
     e = dev_batch_run(h, kind, cur_rule, n, item_trial + i0, need_s ? item_nsites + i0 : nullptr,
                       need_b ? item_nbonds + i0 : nullptr, solve ? 1 : 0, Va, g0, leak, itol, tol, itmax,
-                      literal, bo.data(), iout.data(), h->batch_large);
+                      literal, bo.data(), iout.data(), wts ? false : h->batch_large, wts ? &wc : nullptr);
     if (e != hipSuccess) return hip_status(e, who);
     for (int i = 0; i < n; ++i) {
       perc_batch_item& it = out[i0 + i];
@@ -274,7 +325,17 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
         it.span_sites = li.span_sites;
         if (solve) {
           perc_cond_result res{};
-          rc = perc_conductance(h, rule, cur_rule, Va, g0, leak, itol, tol, itmax, &res, nullptr);
+          // the item's weights on the context, after the labeling; cleared
+          // again after the item (the context is left unweighted)
+          if (wts && wts->item_wset)
+            rc = perc_set_bond_weights(h, wts->weights + (size_t)wts->item_wset[i0 + i] * nb, nb);
+          else if (wts)
+            rc = perc_set_conductcalc_weights(h, rule, wts->item_wseed[i0 + i]);
+          if (!rc) rc = perc_conductance(h, rule, cur_rule, Va, g0, leak, itol, tol, itmax, &res, nullptr);
+          if (wts) {
+            const int rc2 = perc_set_bond_weights(h, nullptr, 0);
+            if (!rc) rc = rc2;
+          }
           if (rc) return rc;
           it.gtop = res.gtop;
           it.gbot = res.gbot;
@@ -398,7 +459,7 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
                            int ntrials, const int* site_src, const int* bond_src, int nitems,
                            const int* item_trial, const int* item_nsites, const int* item_nbonds,
                            int solve, double Va, double g0, double leak, int itol, double tol, int itmax,
-                           perc_batch_item* out) {
+                           perc_batch_item* out, const BatchWeights* wts = nullptr) {
   if (!h) return PERC_EINVAL;
   auto bad = [who](const char* text) {
     set_error(std::string(who) + ": " + text);
@@ -415,7 +476,11 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
   if (ntrials < 0 || nitems < 0) return bad("ntrials or nitems < 0");
   if (itmax < 0) return bad("itmax < 0");
   if (solve && itol != 1 && itol != 2) return bad("itol 1 or 2 only");
-  if (h->batch_large) {
+  if (wts) {  // its own kernel: the perc_set_batch_large flag is not read
+    if (!batch_w_supported(h->g, kind))
+      return bad("lattice not supported by the weighted batch kernel for this kind "
+                 "(perc_batch_weighted_supported)");
+  } else if (h->batch_large) {
     if (!batch_large_supported(h->g, kind))
       return bad("lattice not supported by the large batch kernel for this kind "
                  "(perc_batch_large_supported)");
@@ -448,13 +513,14 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
     }
     return batch_run_items_kind(h, kind, cur_rule, nullptr, nullptr, nitems, item_trial, item_nsites,
                                 item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, site_src,
-                                bond_src);
+                                bond_src, wts);
   }
   int rc = need_b ? batch_upload_orders(h, ntrials, bond_src) : PERC_OK;
   if (!rc && need_s) rc = batch_upload_site_orders(h, ntrials, site_src);
   if (rc) return rc;
   return batch_run_items_kind(h, kind, cur_rule, site_src, bond_src, nitems, item_trial, item_nsites,
-                              item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out);
+                              item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, nullptr, nullptr,
+                              wts);
 }
 
 int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, const int* site_orders,
@@ -474,6 +540,59 @@ int perc_batch_cond_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int nt
   return batch_cond_impl("perc_batch_cond_seeded", true, h, kind, rule, cur_rule, ntrials, site_seeds,
                          bond_seeds, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
                          itol, tol, itmax, out);
+}
+
+int perc_batch_weighted_supported(int kind, int lattice, int m, int n, int pbc) {
+  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND) return 0;
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n > kBatchLargeSites) return 0;
+  return batch_w_supported(make_geom(lattice, m, n, pbc), kind) ? 1 : 0;
+}
+
+int perc_batch_cond_weighted(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials,
+                             const int* site_orders, const int* bond_orders, int nitems,
+                             const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                             int nwsets, const double* weights, const int* item_wset,
+                             const unsigned int* item_wseed, int solve, double Va, double g0, double leak,
+                             int itol, double tol, int itmax, perc_batch_item* out) {
+  if (!h) return PERC_EINVAL;
+  auto bad = [](const char* text) {
+    set_error(std::string("perc_batch_cond_weighted: ") + text);
+    return PERC_EINVAL;
+  };
+  if ((weights != nullptr) != (item_wset != nullptr))
+    return bad("weights and item_wset go together: one of them is missing");
+  const bool expl = weights != nullptr;
+  if (expl && item_wseed) return bad("both weight inputs given: (weights, item_wset) or item_wseed, not both");
+  if (!expl && !item_wseed) return bad("no weight input: (weights, item_wset) or item_wseed");
+  if (expl && nwsets < 1) return bad("nwsets < 1");
+  if (nitems < 0) return bad("ntrials or nitems < 0");
+  if (expl)
+    for (int i = 0; i < nitems; ++i)
+      if (item_wset[i] < 0 || item_wset[i] >= nwsets) return bad("item_wset outside 0..nwsets-1");
+  BatchWeights wts;
+  wts.nwsets = expl ? nwsets : 0;
+  wts.weights = weights;
+  wts.item_wset = item_wset;
+  wts.item_wseed = item_wseed;
+  return batch_cond_impl("perc_batch_cond_weighted", false, h, kind, rule, cur_rule, ntrials, site_orders,
+                         bond_orders, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
+                         itol, tol, itmax, out, &wts);
+}
+
+int perc_batch_twister(perc_ctx* h, int nseeds, const unsigned int* seeds, long long n, double* out) {
+  if (!h) return PERC_EINVAL;
+  if (nseeds < 0 || n < 0) {
+    set_error("perc_batch_twister: nseeds or n < 0");
+    return PERC_EINVAL;
+  }
+  if (nseeds == 0 || n == 0) return PERC_OK;
+  if (!seeds || !out) {
+    set_error("perc_batch_twister: seeds or out missing");
+    return PERC_EINVAL;
+  }
+  hipSetDevice(h->device);
+  return hip_status(dev_batch_twister(h, nseeds, seeds, n, out), "perc_batch_twister");
 }
 
 int perc_shuffle_device_supported(int N) { return shuffle_supported(N) ? 1 : 0; }

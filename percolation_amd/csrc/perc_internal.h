@@ -266,6 +266,7 @@ struct perc_ctx {
   void* batch = nullptr;   // perc_batch_bondc's device buffers (perc_batch.hip), made on first use
   bool batch_large = false;  // perc_set_batch_large: the batch calls run k_batch_cond_large
   int large_lds[2][3] = {};  // dynamic LDS granted per instantiation of it
+  int w_lds[3][2][3] = {};   // ... of k_batch_cond_w (perc_batch_weighted.hip)
   void* scan = nullptr;    // perc_batch_scan's device buffers (perc_batch_scan.hip), made on first use
   void* shuffle = nullptr; // perc_batch_shuffle's device buffers (perc_batch_shuffle.hip), made on first use
 };

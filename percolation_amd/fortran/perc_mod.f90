@@ -382,6 +382,38 @@ module perc_api
       real(c_double), value :: Va, g0, leak, tol
     end function perc_batch_cond_seeded
 
+    ! host-only: 1 when the weighted batch kernel can run this kind on this lattice
+    integer(c_int) function perc_batch_weighted_supported(kind, lattice, m, n, pbc) &
+        bind(C, name='perc_batch_weighted_supported')
+      import :: c_int
+      integer(c_int), value :: kind, lattice, m, n, pbc
+    end function perc_batch_weighted_supported
+
+    ! perc_batch_cond with per-bond conductance multipliers (ConductCalc.m
+    ! condtype 2): explicit rows (weights: nwsets x nb doubles, item_wset) or
+    ! one rand('twister') seed per item (item_wseed), the other input
+    ! c_null_ptr; every list and out (perc_batch_item records) as pointers
+    integer(c_int) function perc_batch_cond_weighted(h, kind, rule, cur_rule, ntrials, site_orders, &
+        bond_orders, nitems, item_trial, item_nsites, item_nbonds, nwsets, weights, item_wset, &
+        item_wseed, solve, Va, g0, leak, itol, tol, itmax, out) &
+        bind(C, name='perc_batch_cond_weighted')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h, site_orders, bond_orders, item_trial, item_nsites, item_nbonds
+      type(c_ptr), value :: weights, item_wset, item_wseed, out
+      integer(c_int), value :: kind, rule, cur_rule, ntrials, nitems, nwsets, solve, itol, itmax
+      real(c_double), value :: Va, g0, leak, tol
+    end function perc_batch_cond_weighted
+
+    ! the device generator on its own: n genrand_res53 doubles per seed
+    ! (seeds: nseeds unsigned 32-bit words; out: nseeds rows of n doubles)
+    integer(c_int) function perc_batch_twister(h, nseeds, seeds, n, out) &
+        bind(C, name='perc_batch_twister')
+      import :: c_int, c_ptr, c_long_long
+      type(c_ptr), value :: h, seeds, out
+      integer(c_int), value :: nseeds
+      integer(c_long_long), value :: n
+    end function perc_batch_twister
+
     integer(c_int) function perc_ensemble_bond_cond(e, ntrials, tseed, npts, nbarr, Va, g0, &
         tol, itmax, nrows, gbot, gtop, iters, bf_c, perccln, stats) &
         bind(C, name='perc_ensemble_bond_cond')

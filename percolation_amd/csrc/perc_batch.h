@@ -1,8 +1,14 @@
 // perc_batch.h -- the batch path of libperc: many independent small
 // realisations (bond, site or mixed) in one launch, one workgroup per
-// (trial, counts) item (perc_batch.hip: k_batch_cond; perc_batch_host.cpp:
-// the C-ABI and the ensemble's batched trial loop).
+// (trial, counts) item.  Who owns what: perc_batch.hip the device buffers,
+// dev_batch_run and k_batch_cond; perc_batch_large.hip and
+// perc_batch_weighted.hip their kernel and its launch; perc_batch_item.h the
+// device code the three kernels share (the item's front end, the workgroup
+// sums, the electrode rows' currents); perc_batch_host.cpp the C-ABI, the LDS
+// plans and the ensemble's batched trial loop.
 #pragma once
+#include <type_traits>
+
 #include "perc_internal.h"
 
 namespace perc {
@@ -20,15 +26,63 @@ struct BatchOut {
   int fallback, pad;
 };
 
+// What every conductance kernel takes (dev_batch_run fills it once): the
+// lattice, the trials' rank arrays, the items, the outputs and the solve's
+// parameters.  A kernel's argument block is this plus its own LDS plan.
+struct BatchItemArgs {
+  Geom g;
+  int N, nb;
+  const int* bond_first;
+  const StencilForms* forms;
+  const int* rank;    // ntrials x nb (bond and mixed kinds)
+  const int* rank_s;  // ntrials x t (site and mixed kinds)
+  const int* item_trial;
+  const int* item_count;   // occupied entries of the bond order (bond and mixed kinds)
+  const int* item_nsites;  // ... of the site order (site and mixed kinds)
+  BatchOut* out;
+  double* iout;  // nitems x 2m
+  int* sflag;
+  int fast, fl, fr, bf_closed;
+  int solve, itol, itmax, cur_rule;
+  double Va, g0, leak, tol;
+};
+
+// The run-time (kind, literal) pair as compile-time constants:
+// f(std::bool_constant<LIT>, std::integral_constant<int, KIND>)
+template <class F>
+hipError_t dispatch_kind_order(int kind, bool literal, F&& f) {
+  auto of = [&](auto lit) {
+    if (kind == PERC_BOND) return f(lit, std::integral_constant<int, PERC_BOND>{});
+    if (kind == PERC_SITE) return f(lit, std::integral_constant<int, PERC_SITE>{});
+    return f(lit, std::integral_constant<int, PERC_SITEBOND>{});
+  };
+  return literal ? of(std::true_type{}) : of(std::false_type{});
+}
+// ... and a workgroup size of 256 / 512 / 1024 with its slot 0 / 1 / 2:
+// f(std::integral_constant<int, NT>, slot)
+template <class F>
+hipError_t dispatch_threads(int nt, F&& f) {
+  if (nt == 256) return f(std::integral_constant<int, 256>{}, 0);
+  if (nt == 512) return f(std::integral_constant<int, 512>{}, 1);
+  return f(std::integral_constant<int, 1024>{}, 2);
+}
+
+// The labeling view every conductance kernel's arena starts with (byte
+// offsets, multiples of 16): parent (int, t + 1) at 0, the bond occupancy
+// (nb + 1 bytes), the member flags (t + 1), the spanning flags (m + 1) and,
+// for the site and mixed kinds, one byte per site (socc, t + 1; the bond
+// kind's layout has none: oSocc = 0, unused).  label_end: its size.
+struct BatchLabelView {
+  int oBocc, oMem, oFlag, oSocc, label_end;
+};
+BatchLabelView batch_label_view(const Geom& g, int kind);
+
 // Byte offsets of the workgroup's LDS arena (every offset a multiple of 16).
-// The solver's p and q (8 N bytes each) start the arena; the labeling's
-// arrays -- parent (int, t + 1), the bond occupancy (nb + 1 bytes), the
-// member and spanning flags -- alias them: they are dead once the row codes,
+// The solver's p and q (8 N bytes each) start the arena; the labeling view
+// (batch_label_view) aliases them: its arrays are dead once the row codes,
 // the top row's rhs and the electrode rows' current codes are formed, before
-// the first iteration writes p.  The site and mixed kinds add one byte per
-// site (socc, t + 1 bytes) to the labeling view, after the spanning flags;
-// the bond kind's layout has none (oSocc = 0, unused).  The row codes follow
-// whichever view ends later.
+// the first iteration writes p.  The row codes follow whichever view ends
+// later.
 struct BatchLds {
   int oQ, oBocc, oMem, oFlag, oSocc, oC, oRed, oOff, oF, oRhs, oCur, oInt, total;
 };
@@ -99,9 +153,9 @@ constexpr int kBatchLargeThreads = 1024;
 constexpr int kBatchLargeEPT = 16;  // rows per thread, at most
 // Byte offsets of its LDS arena (every offset a multiple of 16).  Solver
 // view: p (8 N) at 0, x of the first and last m rows (16 m), the literal
-// order's staging row (two sums x 1024 terms).  The labeling view of
-// batch_lds (parent at 0, bocc, member, flags, socc) aliases it and is dead
-// after the barrier that follows the assembly.  The reduction scratch, the
+// order's staging row (two sums x 1024 terms).  The labeling view
+// (batch_label_view) aliases it and is dead after the barrier that follows
+// the assembly.  The reduction scratch, the
 // form table, the current codes and the counters follow whichever view ends
 // later.
 struct BatchLargeLds {
@@ -110,29 +164,9 @@ struct BatchLargeLds {
 BatchLargeLds batch_large_lds(const Geom& g, int kind);
 // host-only check of perc_batch_large_supported
 bool batch_large_supported(const Geom& g, int kind);
-// what dev_batch_run hands the large kernel (k_batch_cond's arguments with
-// this kernel's LDS plan)
-struct BatchLargeArgs {
-  Geom g;
-  int N, nb;
-  const int* bond_first;
-  const StencilForms* forms;
-  const int* rank;
-  const int* rank_s;
-  const int* item_trial;
-  const int* item_count;
-  const int* item_nsites;
-  BatchOut* out;
-  double* iout;
-  int* sflag;
-  int fast, fl, fr, bf_closed;
-  int solve, itol, itmax, cur_rule;
-  double Va, g0, leak, tol;
-  BatchLargeLds L;
-};
 // one launch of k_batch_cond_large<literal, kind> over nitems items on the
-// context's stream (a.L filled here)
-hipError_t dev_batch_large_launch(perc_ctx* h, int kind, bool literal, BatchLargeArgs a, int nitems);
+// context's stream
+hipError_t dev_batch_large_launch(perc_ctx* h, int kind, bool literal, const BatchItemArgs& c, int nitems);
 // ---- per-bond weights (perc_batch_weighted.hip: k_batch_cond_w) ---------
 // k_batch_cond_large's scheme (p alone of the N-sized solver arrays in LDS,
 // r, the diagonal, q and the form / count of a thread's own rows in its
@@ -147,8 +181,8 @@ constexpr int kBatchWRows = 1024 * kBatchWEPT;
 int batch_w_threads(int N);
 // Byte offsets of its LDS arena (every offset a multiple of 16).  Solver
 // view: p (8 N) at 0, x of the first and last m rows (16 m), the literal
-// order's staging row (two sums x NT terms).  The labeling view of batch_lds
-// aliases it.  After whichever view ends later, outside both: the slot values
+// order's staging row (two sums x NT terms).  The labeling view
+// (batch_label_view) aliases it.  After whichever view ends later, outside both: the slot values
 // (scn arrays of 8 N bytes; the assembly writes them while it still reads
 // parent and bocc), the electrode rows' slot values (2m sites x 6 doubles),
 // the reduction scratch, the form table and 32 counters.
@@ -167,37 +201,22 @@ struct BatchWeights {
   const int* item_wset = nullptr;
   const unsigned* item_wseed = nullptr;
 };
-// what dev_batch_run hands the weighted kernel: k_batch_cond_large's
-// arguments, and per item either its weight row (wrows + item_wset[i] * nb)
-// or its draws (u + i * nb, from k_twister_stream) and its row of the
-// launch's scratch (wscratch + i * wstride; wstride = nb rounded up to 16
-// doubles, so that no two workgroups write one 128-byte line)
-struct BatchWArgs {
-  Geom g;
-  int N, nb;
-  const int* bond_first;
-  const StencilForms* forms;
-  const int* rank;
-  const int* rank_s;
-  const int* item_trial;
-  const int* item_count;
-  const int* item_nsites;
-  const int* item_wset;   // explicit mode, else NULL
-  const double* wrows;
-  const double* u;        // ConductCalc mode
-  double* wscratch;
-  int wstride;
-  BatchOut* out;
-  double* iout;
-  int* sflag;
-  int fast, fl, fr, bf_closed;
-  int solve, itol, itmax, cur_rule;
-  double Va, g0, leak, tol;
-  BatchWLds L;
+// what dev_batch_run hands the weighted kernel beside the common block: per
+// item either its weight row (wrows + item_wset[i] * nb) or its draws
+// (u + i * nb, from k_twister_stream) and its row of the launch's scratch
+// (wscratch + i * wstride; wstride = nb rounded up to 16 doubles, so that no
+// two workgroups write one 128-byte line)
+struct BatchWItems {
+  const int* item_wset = nullptr;  // explicit mode, else NULL
+  const double* wrows = nullptr;
+  const double* u = nullptr;       // ConductCalc mode
+  double* wscratch = nullptr;
+  int wstride = 0;
 };
 // one launch of k_batch_cond_w<threads, literal, kind> over nitems items on
-// the context's stream (a.L filled here)
-hipError_t dev_batch_w_launch(perc_ctx* h, int kind, bool literal, BatchWArgs a, int nitems);
+// the context's stream
+hipError_t dev_batch_w_launch(perc_ctx* h, int kind, bool literal, const BatchItemArgs& c,
+                              const BatchWItems& w, int nitems);
 // k_twister_stream: n genrand_res53 doubles per seed (d_seeds, d_out: device)
 hipError_t dev_twister_launch(perc_ctx* h, int nseeds, const unsigned* d_seeds, long long n, double* d_out);
 // perc_batch_twister: seeds and out on the host, through the batch buffers

@@ -6,31 +6,16 @@
 // assemble_row, k_cg_small's loop (both dot orders) and k_currents' per-site
 // expression.  Many items per launch: the ensemble's (trial, grid point)
 // pairs side by side instead of a dozen launches and one busy CU each.
-#include <climits>
-
-#include "perc_asm_row.h"
-#include "perc_batch.h"
-#include "perc_batch_uf.h"
+// The front end, the workgroup sum and the currents are perc_batch_item.h's,
+// shared with k_batch_cond_large and k_batch_cond_w; this file keeps the
+// kernel's assembly and CG loop, the batch path's device buffers and
+// dev_batch_run, which fills the common argument block for all three.
+#include "perc_batch_item.h"
 
 namespace perc {
 namespace {
 
-struct BatchArgs {
-  Geom g;
-  int N, nb;
-  const int* bond_first;
-  const StencilForms* forms;
-  const int* rank;    // ntrials x nb (bond and mixed kinds)
-  const int* rank_s;  // ntrials x t (site and mixed kinds)
-  const int* item_trial;
-  const int* item_count;   // occupied entries of the bond order (bond and mixed kinds)
-  const int* item_nsites;  // ... of the site order (site and mixed kinds)
-  BatchOut* out;
-  double* iout;  // nitems x 2m
-  int* sflag;
-  int fast, fl, fr, bf_closed;
-  int solve, itol, itmax, cur_rule;
-  double Va, g0, leak, tol;
+struct BatchArgs : BatchItemArgs {
   BatchLds L;
 };
 
@@ -51,11 +36,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int item = blockIdx.x;
   // labeling view of the arena
-  int* parent = reinterpret_cast<int*>(smem);
-  uint8_t* bocc = reinterpret_cast<uint8_t*>(smem + a.L.oBocc);
-  uint8_t* member = reinterpret_cast<uint8_t*>(smem + a.L.oMem);
-  uint8_t* flag = reinterpret_cast<uint8_t*>(smem + a.L.oFlag);
-  uint8_t* socc = KIND != PERC_BOND ? reinterpret_cast<uint8_t*>(smem + a.L.oSocc) : nullptr;
+  const LabelArrays lv = label_arrays<KIND>(smem, a.L.oBocc, a.L.oMem, a.L.oFlag, a.L.oSocc);
   // solver view
   double* s_p = reinterpret_cast<double*>(smem);
   double* s_q = reinterpret_cast<double*>(smem + a.L.oQ);
@@ -67,104 +48,10 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
   uint16_t* s_cur = reinterpret_cast<uint16_t*>(smem + a.L.oCur);
   int* s_i = reinterpret_cast<int*>(smem + a.L.oInt);
 
-  const int trial = a.item_trial[item];
-  const int count = KIND != PERC_SITE ? a.item_count[item] : 0;
-  const int nsite = KIND != PERC_BOND ? a.item_nsites[item] : 0;
-  const int* __restrict__ rank = KIND != PERC_SITE ? a.rank + (size_t)trial * a.nb : nullptr;
-  const int* __restrict__ rank_s = KIND != PERC_BOND ? a.rank_s + (size_t)trial * T : nullptr;
-  BatchOut* out = a.out + item;
-
-  // ---- occupancy: an element is occupied iff its position in its order <
-  // its count.  Site kinds: the member flag is the occupied site (perc_cc.h);
-  // the site kind reads no bond ranks, bocc is all zero as perc_label leaves it
-  {
-    const int nw = (int)(sizeof(StencilForms) / 4);
-    const int* src = reinterpret_cast<const int*>(a.forms);
-    int* dst = reinterpret_cast<int*>(sF);
-    for (int k = t; k < nw; k += NT) dst[k] = src[k];
-  }
-  if (t < 8) s_i[t] = t == 2 ? INT_MAX : 0;
-  for (int s = t; s <= T; s += NT) {
-    parent[s] = s;
-    if constexpr (KIND == PERC_BOND) {
-      member[s] = 0;
-    } else {
-      const uint8_t o = s >= 1 && rank_s[s - 1] < nsite ? 1 : 0;
-      socc[s] = o;
-      member[s] = o;
-    }
-  }
-  for (int c = t; c <= m; c += NT) flag[c] = 0;
-  if constexpr (KIND == PERC_SITE) {
-    for (int id = t; id < a.nb; id += NT) bocc[id] = 0;
-  } else {
-    for (int id = t; id < a.nb; id += NT) bocc[id] = rank[id] < count ? 1 : 0;
-  }
-  load_forms(*a.forms, s_off);  // (ends with a workgroup barrier)
-
-  // ---- labeling: hook the larger root under the smaller over every bond
-  // that connects (cc_link's rule of the kind), flatten, until a pass hooks
-  // nothing (lds_label)
-  lds_label<NT>(g, a.bond_first, parent, [&](int pass, int s, int, int q, int id) {
-    if constexpr (KIND == PERC_BOND) {
-      if (!bocc[id]) return false;
-      if (pass == 0) {
-        member[s] = 1;
-        member[q] = 1;
-      }
-      return true;
-    } else if constexpr (KIND == PERC_SITE) {
-      return socc[s] && socc[q];
-    } else {
-      return bocc[id] && socc[s] && socc[q];
-    }
-  });
-
-  // ---- spanning (k_span_top's rule): root <= m and a top-row member
-  for (int c = t; c < m; c += NT) {
-    const int s = T - m + 1 + c;
-    if (member[s] && parent[s] <= m) flag[parent[s]] = 1;
-  }
-  __syncthreads();
-  {
-    int ncl = 0, nsp = 0, mn = INT_MAX;
-    for (int s = t + 1; s <= T; s += NT) ncl += parent[s] == s && member[s];
-    for (int c = t + 1; c <= m; c += NT)
-      if (flag[c]) {
-        ++nsp;
-        mn = min(mn, c);
-      }
-    if (ncl) atomicAdd(&s_i[0], ncl);
-    if (nsp) {
-      atomicAdd(&s_i[1], nsp);
-      atomicMin(&s_i[2], mn);
-    }
-  }
-  __syncthreads();
-  const int nclusters = s_i[0], nspan = s_i[1];
-  const int root = nspan > 0 ? s_i[2] : 0;
-  if (root) {
-    int cnt = 0;
-    for (int s = t + 1; s <= T; s += NT) cnt += member[s] && parent[s] == root;
-    if (cnt) atomicAdd(&s_i[3], cnt);
-  }
-  __syncthreads();
-  const int span_sites = s_i[3];
-  const bool stop = nspan != 1 || !a.solve;  // (uniform: LDS values after a barrier)
-  if (t == 0) {
-    out->nclusters = nclusters;
-    out->nspan = nspan;
-    out->span_root = root;
-    out->span_sites = span_sites;
-    out->fallback = nspan > 1 ? 1 : 0;  // the lowest-label rule: host replay
-    out->pad = 0;
-    if (stop) {
-      out->status = nspan == 0 ? 1 : 0;
-      out->iter = 0;
-      out->err = 0.0;
-    }
-  }
-  if (stop) return;
+  // ---- occupancy, labeling, spanning, the item's header (perc_batch_item.h)
+  const BatchFront front = batch_front<NT, KIND>(a, g, lv, sF, s_off, s_i);
+  if (front.stop) return;
+  const int root = front.root;
 
   // ---- assembly: row codes into LDS, the top system row's rhs (the only
   // rows with a non-zero one), the electrode rows' slot values as 2-bit codes
@@ -173,29 +60,13 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
   for (int i = t; i < N; i += NT) {
     uint16_t c;
     double b;
-    assemble_row_vals<false>(g, i, a.bond_first, bocc, socc, parent, nullptr, nullptr, nullptr, &b,
+    assemble_row_vals<false>(g, i, a.bond_first, lv.bocc, lv.socc, lv.parent, nullptr, nullptr, nullptr, &b,
                              &c, a.sflag, *sF, a.fast, a.fl, a.fr, a.bf_closed, RULE, g0, leak, Va,
                              root, nullptr);
     s_c[i] = c;
     if (i >= N - m) s_rhs[i - (N - m)] = b;
   }
-#pragma unroll 1
-  for (int idx = t; idx < 2 * m; idx += NT) {
-    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
-    const int ps = parent[s];
-    int nbr[6];
-    const int cnt = sorted_neighbours(g, s, nbr);
-    unsigned cc = 0;
-    for (int j = 0; j < cnt; ++j) {
-      const int c = nbr[j];
-      const int id = s < c ? bond_id(g, a.bond_first, s, c) : bond_id(g, a.bond_first, c, s);
-      unsigned kind = 0;  // no bond: 0.0 (k_currents)
-      if (id >= 0)
-        kind = bond_value(RULE, id, s, c, ps, bocc, socc, root, g0, leak, nullptr) == -g0 ? 2u : 1u;
-      cc |= kind << (2 * j);
-    }
-    s_cur[idx] = (uint16_t)cc;
-  }
+  encode_electrode_rows<NT, RULE>(g, a.bond_first, lv, root, g0, leak, s_cur);
   __syncthreads();  // the labeling arrays are dead from here: p and q take their place
 
   // ---- solve: k_cg_small<true, LIT>, the prologue included (x = 0, r = b)
@@ -213,24 +84,6 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
     xv[j] = 0.0;
     dv[j] = i < N ? code_diag(c, ng0, nleak) : 1.0;
   }
-  // workgroup sum: per-wave butterfly, then the waves in order
-  auto wg_sum = [&](double v0, double v1, double* o0, double* o1) {
-    v0 = wave_sum(v0);
-    v1 = wave_sum(v1);
-    if (lane == 0) {
-      s_red[wid] = v0;
-      s_red[16 + wid] = v1;
-    }
-    __syncthreads();
-    double t0 = s_red[0], t1 = s_red[16];
-    for (int w = 1; w < NT / 64; ++w) {
-      t0 = t0 + s_red[w];
-      t1 = t1 + s_red[16 + w];
-    }
-    __syncthreads();  // s_red reuse
-    *o0 = t0;
-    *o1 = t1;
-  };
   const int itol = a.itol, itmax = a.itmax;
   const double tol = a.tol;
   double bnrm, bknum;
@@ -272,7 +125,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
       }
     }
     double tb, tz;
-    wg_sum(b2, zr0, &tb, &tz);
+    wg_sum2<NT>(s_red, b2, zr0, &tb, &tz);
     bnrm = sqrt(tb);
     bknum = tz;
   }
@@ -325,7 +178,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
       akden = s_red[32];
       __syncthreads();
     } else {
-      wg_sum(dot, 0.0, &akden, &unused);
+      wg_sum2<NT>(s_red, dot, 0.0, &akden, &unused);
     }
     ak = bknum / akden;
     // x += ak p, r -= ak q, z = r/d, z.r and r.r (linbcg :801-806, 808-813)
@@ -370,7 +223,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
       trr = s_red[33];
       __syncthreads();
     } else {
-      wg_sum(zr, rr, &tzr, &trr);
+      wg_sum2<NT>(s_red, zr, rr, &tzr, &trr);
     }
     err = sqrt(trr) / bnrm;
     bk = tzr / bknum;
@@ -389,41 +242,16 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
   __syncthreads();
   const double* x = s_q;
   double* iout = a.iout + (size_t)item * 2 * m;
+  auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : x[c - m - 1]); };
 #pragma unroll 1
   for (int idx = t; idx < 2 * m; idx += NT) {
-    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
-    int nbr[6];
-    const int cnt = sorted_neighbours(g, s, nbr);
     const unsigned cc = s_cur[idx];
-    double gv[6];
-    double rowsum = 0.0;
-    for (int j = 0; j < cnt; ++j) {
-      const unsigned kind = (cc >> (2 * j)) & 3u;
-      gv[j] = kind == 0 ? 0.0 : (kind == 2 ? -g0 : -leak);
-      rowsum = rowsum + gv[j];
-    }
-    const double d = -rowsum;
-    auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : x[c - m - 1]); };
-    double acc;
-    if (a.cur_rule == PERC_CUR_FORTRAN) {
-      acc = d * V(s);
-      for (int j = 0; j < cnt; ++j)
-        if (fabs(gv[j]) >= 1.0e-10) acc = acc + gv[j] * V(nbr[j]);
-    } else {  // no threshold, the diagonal term before the first neighbour > s
-      acc = 0.0;
-      bool done = false;
-      for (int j = 0; j < cnt; ++j) {
-        if (!done && nbr[j] > s) {
-          acc = acc + d * V(s);
-          done = true;
-        }
-        acc = acc + gv[j] * V(nbr[j]);
-      }
-      if (!done) acc = acc + d * V(s);
-    }
-    iout[idx] = acc;
+    iout[idx] = electrode_current(
+        g, electrode_site(g, idx), a.cur_rule,
+        [&](int j) -> double { return electrode_code_value(cc, j, g0, leak); }, V);
   }
   if (t == 0) {
+    BatchOut* out = a.out + item;
     out->status = 0;
     out->iter = k;
     out->err = err;
@@ -453,51 +281,9 @@ struct BatchState {
   size_t wsrc_cap = 0, wscr_cap = 0, wsel_cap = 0;
 };
 
-// *p grown to n elements (capacity *cap); the contents are not kept
-template <class T>
-hipError_t grow(T** p, size_t* cap, size_t n) {
-  if (*cap >= n) return hipSuccess;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(dmalloc(p, n));
-  *cap = n;
-  return hipSuccess;
-}
-
-template <int NT, bool LIT, int KIND>
-hipError_t launch(BatchState* B, int slot, const BatchArgs& a, int nitems, hipStream_t st) {
-  if (B->lds_attr[slot][LIT][KIND] < a.L.total) {  // dynamic LDS beyond the default limit
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_cond<NT, LIT, KIND>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
-    B->lds_attr[slot][LIT][KIND] = a.L.total;
-  }
-  k_batch_cond<NT, LIT, KIND><<<nitems, NT, a.L.total, st>>>(a);
-  return dbg_sync(st, "k_batch_cond");
-}
-
-template <int NT>
-hipError_t launch_kind(BatchState* B, int slot, int kind, bool literal, const BatchArgs& a, int nitems,
-                       hipStream_t st) {
-  if (kind == PERC_BOND)
-    return literal ? launch<NT, true, PERC_BOND>(B, slot, a, nitems, st)
-                   : launch<NT, false, PERC_BOND>(B, slot, a, nitems, st);
-  if (kind == PERC_SITE)
-    return literal ? launch<NT, true, PERC_SITE>(B, slot, a, nitems, st)
-                   : launch<NT, false, PERC_SITE>(B, slot, a, nitems, st);
-  return literal ? launch<NT, true, PERC_SITEBOND>(B, slot, a, nitems, st)
-                 : launch<NT, false, PERC_SITEBOND>(B, slot, a, nitems, st);
-}
-
 // a rank array of n ints in *p (capacity *cap), copied from the host
 hipError_t upload_ranks(int** p, size_t* cap, size_t n, const int* rank, hipStream_t st) {
-  if (*cap < n) {
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(dmalloc(p, n));
-    *cap = n;
-  }
+  HIP_TRY(grow(p, cap, n));
   if (n) HIP_TRY(hipMemcpyAsync(*p, rank, sizeof(int) * n, hipMemcpyHostToDevice, st));
   return hipStreamSynchronize(st);  // (the caller's array may go away)
 }
@@ -545,13 +331,7 @@ hipError_t dev_batch_reserve(perc_ctx* h, int list, int ntrials, int** d_rank) {
   int* have = bonds ? &B->ntrials : &B->ntrials_s;
   const size_t n = (size_t)ntrials * (size_t)(bonds ? h->nb : h->g.t);
   *have = 0;
-  if (*cap < n) {
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(dmalloc(p, n));
-    *cap = n;
-  }
+  HIP_TRY(grow(p, cap, n));
   *have = ntrials;
   *d_rank = *p;
   return hipSuccess;
@@ -614,24 +394,15 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
     HIP_TRY(dmalloc(&B->d_sflag, 4));
     HIP_TRY(hipMemsetAsync(B->d_sflag, 0, 4 * sizeof(int), st));
   }
-  if (B->item_cap < (size_t)nitems) {
-    if (B->d_items) HIP_TRY(hipFree(B->d_items));
-    if (B->d_out) HIP_TRY(hipFree(B->d_out));
-    B->d_items = nullptr;
-    B->d_out = nullptr;
+  if (B->item_cap < (size_t)nitems) {  // d_items and d_out share one capacity
+    size_t c3 = 0, c1 = 0;  // zero on purpose: grow() frees and allocates both afresh
     B->item_cap = 0;
-    HIP_TRY(dmalloc(&B->d_items, 3 * (size_t)nitems));
-    HIP_TRY(dmalloc(&B->d_out, (size_t)nitems));
+    HIP_TRY(grow(&B->d_items, &c3, 3 * (size_t)nitems));
+    HIP_TRY(grow(&B->d_out, &c1, (size_t)nitems));
     B->item_cap = nitems;
   }
   const size_t niout = solve ? (size_t)nitems * 2 * m : 0;
-  if (B->iout_cap < niout) {
-    if (B->d_iout) HIP_TRY(hipFree(B->d_iout));
-    B->d_iout = nullptr;
-    B->iout_cap = 0;
-    HIP_TRY(dmalloc(&B->d_iout, niout));
-    B->iout_cap = niout;
-  }
+  HIP_TRY(grow(&B->d_iout, &B->iout_cap, niout));
   HIP_TRY(hipMemcpyAsync(B->d_items, item_trial, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
   if (need_b)
     HIP_TRY(hipMemcpyAsync(B->d_items + nitems, item_count, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
@@ -640,39 +411,34 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
                            hipMemcpyHostToDevice, st));
   // an item that stops before the currents leaves its iout row unwritten
   if (niout) HIP_TRY(hipMemsetAsync(B->d_iout, 0, sizeof(double) * niout, st));
-  BatchArgs a;
-  a.g = h->g;
-  a.N = h->N;
-  a.nb = (int)h->nb;
-  a.bond_first = h->d.bond_first;
-  a.forms = h->d.forms_dev;
-  a.rank = B->d_rank;
-  a.rank_s = B->d_rank_s;
-  a.item_trial = B->d_items;
-  a.item_count = B->d_items + nitems;
-  a.item_nsites = B->d_items + 2 * (size_t)nitems;
-  a.out = B->d_out;
-  a.iout = B->d_iout;
-  a.sflag = B->d_sflag;
-  asm_closed_forms(h, &a.fast, &a.fl, &a.fr);
-  a.bf_closed = h->bf_closed ? 1 : 0;
-  a.solve = solve;
-  a.itol = itol;
-  a.itmax = itmax;
-  a.cur_rule = cur_rule;
-  a.Va = Va;
-  a.g0 = g0;
-  a.leak = leak;
-  a.tol = tol;
-  a.L = batch_lds(h->g, kind);
-  const int nt = batch_threads(h->N);
+  BatchItemArgs c;
+  c.g = h->g;
+  c.N = h->N;
+  c.nb = (int)h->nb;
+  c.bond_first = h->d.bond_first;
+  c.forms = h->d.forms_dev;
+  c.rank = B->d_rank;
+  c.rank_s = B->d_rank_s;
+  c.item_trial = B->d_items;
+  c.item_count = B->d_items + nitems;
+  c.item_nsites = B->d_items + 2 * (size_t)nitems;
+  c.out = B->d_out;
+  c.iout = B->d_iout;
+  c.sflag = B->d_sflag;
+  asm_closed_forms(h, &c.fast, &c.fl, &c.fr);
+  c.bf_closed = h->bf_closed ? 1 : 0;
+  c.solve = solve;
+  c.itol = itol;
+  c.itmax = itmax;
+  c.cur_rule = cur_rule;
+  c.Va = Va;
+  c.g0 = g0;
+  c.leak = leak;
+  c.tol = tol;
   hipError_t e;
-  if (wts) {  // k_batch_cond_w (perc_batch_weighted.hip): the same arguments, its own LDS plan, the weights
-    const size_t nb = (size_t)a.nb;
-    BatchWArgs b{a.g, a.N, a.nb, a.bond_first, a.forms, a.rank, a.rank_s, a.item_trial, a.item_count,
-                 a.item_nsites, nullptr, nullptr, nullptr, nullptr, 0, a.out, a.iout, a.sflag, a.fast, a.fl,
-                 a.fr, a.bf_closed, a.solve, a.itol, a.itmax, a.cur_rule, a.Va, a.g0, a.leak, a.tol,
-                 BatchWLds{}};
+  if (wts) {  // k_batch_cond_w (perc_batch_weighted.hip): the common block and the weights
+    const size_t nb = (size_t)c.nb;
+    BatchWItems b;
     HIP_TRY(grow(&B->d_wsel, &B->wsel_cap, (size_t)nitems));
     if (wts->item_wset) {
       // the rows this launch's items name, each uploaded once, numbered as met
@@ -695,23 +461,25 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
       b.wrows = B->d_wsrc;
     } else {
       HIP_TRY(grow(&B->d_wsrc, &B->wsrc_cap, (size_t)nitems * nb));
-      b.wstride = (a.nb + 15) & ~15;
+      b.wstride = (c.nb + 15) & ~15;
       HIP_TRY(grow(&B->d_wscr, &B->wscr_cap, (size_t)nitems * (size_t)b.wstride));
       HIP_TRY(hipMemcpyAsync(B->d_wsel, wts->item_wseed, sizeof(unsigned) * nitems, hipMemcpyHostToDevice, st));
       HIP_TRY(dev_twister_launch(h, nitems, B->d_wsel, (long long)nb, B->d_wsrc));
       b.u = B->d_wsrc;
       b.wscratch = B->d_wscr;
     }
-    e = dev_batch_w_launch(h, kind, literal, b, nitems);
-  } else if (large) {  // k_batch_cond_large (perc_batch_large.hip): the same arguments, its own LDS plan
-    const BatchLargeArgs b{a.g, a.N, a.nb, a.bond_first, a.forms, a.rank, a.rank_s, a.item_trial,
-                           a.item_count, a.item_nsites, a.out, a.iout, a.sflag, a.fast, a.fl, a.fr,
-                           a.bf_closed, a.solve, a.itol, a.itmax, a.cur_rule, a.Va, a.g0, a.leak, a.tol,
-                           BatchLargeLds{}};
-    e = dev_batch_large_launch(h, kind, literal, b, nitems);
-  } else if (nt == 256) e = launch_kind<256>(B, 0, kind, literal, a, nitems, st);
-  else if (nt == 512) e = launch_kind<512>(B, 1, kind, literal, a, nitems, st);
-  else e = launch_kind<1024>(B, 2, kind, literal, a, nitems, st);
+    e = dev_batch_w_launch(h, kind, literal, c, b, nitems);
+  } else if (large) {  // k_batch_cond_large (perc_batch_large.hip)
+    e = dev_batch_large_launch(h, kind, literal, c, nitems);
+  } else {
+    const BatchArgs a{c, batch_lds(h->g, kind)};
+    e = dispatch_threads(batch_threads(h->N), [&](auto nt, int slot) {
+      return dispatch_kind_order(kind, literal, [&](auto lit, auto kd) {
+        return launch_lds(&k_batch_cond<nt(), lit(), kd()>, &B->lds_attr[slot][lit()][kd()], a, nitems,
+                          nt(), st, "k_batch_cond");
+      });
+    });
+  }
   HIP_TRY(e);
   int flag = 0;
   HIP_TRY(hipMemcpyAsync(out, B->d_out, sizeof(BatchOut) * nitems, hipMemcpyDeviceToHost, st));

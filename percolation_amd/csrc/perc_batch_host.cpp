@@ -22,21 +22,36 @@
 
 namespace perc {
 
+// x rounded up to a multiple of 16 (the arenas' offsets)
+static int up16(long long x) { return (int)((x + 15) & ~15LL); }
+
+BatchLabelView batch_label_view(const Geom& g, int kind) {
+  BatchLabelView V{};
+  V.oBocc = up16(4 * ((long long)g.t + 1));
+  V.oMem = V.oBocc + up16(nbonds(g) + 1);
+  V.oFlag = V.oMem + up16(g.t + 1);
+  V.label_end = V.oFlag + up16(g.m + 1);
+  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
+    V.oSocc = V.label_end;
+    V.label_end = V.oSocc + up16((long long)g.t + 1);
+  }
+  return V;
+}
+
+// the lattices every one-workgroup conductance kernel takes: three rows and
+// columns at least, an even m on the triangular lattice (perc_ctx_create, H7)
+static bool batch_geom_ok(const Geom& g) {
+  return g.n >= 3 && g.m >= 3 && !(g.lattice == kTriangular && (g.m % 2) == 1);
+}
+
 BatchLds batch_lds(const Geom& g, int kind) {
-  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
-  const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
+  const long long N = (long long)g.t - 2 * g.m;
   BatchLds L{};
   L.oQ = up16(8 * N);
   const int solver_end = L.oQ + up16(8 * N);
-  L.oBocc = up16(4 * ((long long)g.t + 1));
-  L.oMem = L.oBocc + up16(nb + 1);
-  L.oFlag = L.oMem + up16(g.t + 1);
-  int label_end = L.oFlag + up16(g.m + 1);
-  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
-    L.oSocc = label_end;
-    label_end = L.oSocc + up16((long long)g.t + 1);
-  }
-  L.oC = std::max(solver_end, label_end);
+  const BatchLabelView V = batch_label_view(g, kind);
+  L.oBocc = V.oBocc, L.oMem = V.oMem, L.oFlag = V.oFlag, L.oSocc = V.oSocc;
+  L.oC = std::max(solver_end, V.label_end);
   L.oRed = L.oC + up16(2 * N);
   L.oOff = L.oRed + up16(48 * sizeof(double));
   L.oF = L.oOff + up16(kMaxForms * kMaxSlots * sizeof(int));
@@ -84,8 +99,7 @@ static bool stencil_rows_ok(const Geom& g) {
 }
 
 bool batch_supported(const Geom& g, int kind) {
-  if (g.n < 3 || g.m < 3) return false;
-  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  if (!batch_geom_ok(g)) return false;
   const long long N = (long long)(g.n - 2) * g.m;
   if (N > kBatchRows) return false;
   if (!stencil_rows_ok(g)) return false;
@@ -94,23 +108,16 @@ bool batch_supported(const Geom& g, int kind) {
 }
 
 BatchLargeLds batch_large_lds(const Geom& g, int kind) {
-  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
-  const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
+  const long long N = (long long)g.t - 2 * g.m;
   BatchLargeLds L{};
   L.oX = up16(8 * N);
   L.oStage = L.oX + up16(16LL * g.m);
   const int solver_end = L.oStage + 2 * kBatchLargeThreads * (int)sizeof(double);
-  L.oBocc = up16(4 * ((long long)g.t + 1));
-  L.oMem = L.oBocc + up16(nb + 1);
-  L.oFlag = L.oMem + up16(g.t + 1);
-  int label_end = L.oFlag + up16(g.m + 1);
-  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
-    L.oSocc = label_end;
-    label_end = L.oSocc + up16((long long)g.t + 1);
-  }
+  const BatchLabelView V = batch_label_view(g, kind);
+  L.oBocc = V.oBocc, L.oMem = V.oMem, L.oFlag = V.oFlag, L.oSocc = V.oSocc;
   // x and the staging row lie in what the labeling view overhangs of p, or
   // past it; what the labeling and the assembly read follows both views
-  L.oRed = std::max(solver_end, label_end);
+  L.oRed = std::max(solver_end, V.label_end);
   L.oOff = L.oRed + up16(48 * sizeof(double));
   L.oF = L.oOff + up16(kMaxForms * kMaxSlots * sizeof(int));
   L.oCur = L.oF + up16(sizeof(StencilForms));
@@ -120,8 +127,7 @@ BatchLargeLds batch_large_lds(const Geom& g, int kind) {
 }
 
 bool batch_large_supported(const Geom& g, int kind) {
-  if (g.n < 3 || g.m < 3) return false;
-  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  if (!batch_geom_ok(g)) return false;
   if ((long long)g.m * g.n > kBatchLargeSites) return false;
   if (!stencil_rows_ok(g)) return false;
   const BatchLargeLds L = batch_large_lds(g, kind);
@@ -131,24 +137,17 @@ bool batch_large_supported(const Geom& g, int kind) {
 int batch_w_threads(int N) { return N <= 256 * kBatchWEPT ? 256 : (N <= 512 * kBatchWEPT ? 512 : 1024); }
 
 BatchWLds batch_w_lds(const Geom& g, int kind) {
-  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
-  const long long N = (long long)g.t - 2 * g.m, nb = nbonds(g);
+  const long long N = (long long)g.t - 2 * g.m;
   const int nt = batch_w_threads((int)std::min<long long>(N, kBatchWRows));
   BatchWLds L{};
   L.oX = up16(8 * N);
   L.oStage = L.oX + up16(16LL * g.m);
   const int solver_end = L.oStage + 2 * nt * (int)sizeof(double);
-  L.oBocc = up16(4 * ((long long)g.t + 1));
-  L.oMem = L.oBocc + up16(nb + 1);
-  L.oFlag = L.oMem + up16(g.t + 1);
-  int label_end = L.oFlag + up16(g.m + 1);
-  if (kind != PERC_BOND) {  // the site occupancy, one byte per site
-    L.oSocc = label_end;
-    label_end = L.oSocc + up16((long long)g.t + 1);
-  }
+  const BatchLabelView V = batch_label_view(g, kind);
+  L.oBocc = V.oBocc, L.oMem = V.oMem, L.oFlag = V.oFlag, L.oSocc = V.oSocc;
   // the slot values are written while the labeling view is still read and
   // read while the solver view is live: past both
-  L.oVal = std::max(solver_end, label_end);
+  L.oVal = std::max(solver_end, V.label_end);
   L.oEl = L.oVal + up16(8LL * g.scn * N);
   L.oRed = L.oEl + up16(8LL * 6 * 2 * g.m);
   L.oOff = L.oRed + up16(48 * sizeof(double));
@@ -159,8 +158,7 @@ BatchWLds batch_w_lds(const Geom& g, int kind) {
 }
 
 bool batch_w_supported(const Geom& g, int kind) {
-  if (g.n < 3 || g.m < 3) return false;
-  if (g.lattice == kTriangular && (g.m % 2) == 1) return false;  // (perc_ctx_create, H7)
+  if (!batch_geom_ok(g)) return false;
   const long long N = (long long)(g.n - 2) * g.m;
   if (N > kBatchWRows) return false;  // kBatchWEPT rows per thread at 1024 threads
   if (!batch_large_supported(g, kind)) return false;  // (its checks, stencil_rows_ok among them)
@@ -169,7 +167,6 @@ bool batch_w_supported(const Geom& g, int kind) {
 }
 
 ScanLds scan_lds(const Geom& g) {
-  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
   ScanLds L{};
   L.oSize = up16(4 * ((long long)g.t + 1));
   L.oLink = L.oSize + up16(4 * ((long long)g.t + 1));
@@ -187,7 +184,6 @@ bool scan_supported(const Geom& g) {
 }
 
 ShuffleLds shuffle_lds(int N) {
-  auto up16 = [](long long x) { return (int)((x + 15) & ~15LL); };
   ShuffleLds L{};
   L.oJ = up16(2 * ((long long)N + 1));
   L.total = L.oJ + 64 * (int)sizeof(int);

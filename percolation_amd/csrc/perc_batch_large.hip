@@ -1,7 +1,7 @@
 // perc_batch_large.hip -- k_batch_cond_large: k_batch_cond's one-workgroup
-// realisation (occupancy from ranks, union-find labeling in LDS, the spanning
-// rule, assemble_row, the CG loop in both dot orders, the currents) for
-// lattices up to 128 x 128.  1024 threads, at most 16 rows per thread.  Of
+// realisation (perc_batch_item.h's front end, sums and currents around this
+// file's assembly and CG loop in both dot orders) for lattices up to
+// 128 x 128.  1024 threads, at most 16 rows per thread.  Of
 // the N-sized solver arrays only p(k) lies in LDS: a thread keeps the u16
 // codes of its own rows in registers (two per VGPR) beside r, x is carried
 // on the 2m rows the currents read, and q never goes to LDS: the fast order
@@ -9,14 +9,14 @@
 // order rebuilds q in the r update from p with the call that formed it for
 // q.p, bitwise the same (the march's way).  Nothing takes this
 // path unless asked (perc_set_batch_large).
-#include <climits>
-
-#include "perc_asm_row.h"
-#include "perc_batch.h"
-#include "perc_batch_uf.h"
+#include "perc_batch_item.h"
 
 namespace perc {
 namespace {
+
+struct BatchLargeArgs : BatchItemArgs {
+  BatchLargeLds L;
+};
 
 constexpr int kLargeNT = kBatchLargeThreads;
 constexpr int kLargeEPT = kBatchLargeEPT;
@@ -32,9 +32,9 @@ constexpr bool kHoldQ = true;
 
 // Rows t, t + 1024, .. per thread.  LIT: the literal dot order -- every sum
 // folded by wave 0 in ascending row order, in rounds of 1024 rows through
-// one staging row in LDS; bitwise k_fold_init + k_cg_small<true, true>.
+// one staging row in LDS (lit_round); bitwise k_fold_init + k_cg_small<true, true>.
 // Else per thread in row order, wave butterfly, waves in order
-// (k_batch_cond's tree).  KIND as k_batch_cond's.
+// (wg_sum2).  KIND as k_batch_cond's.
 template <bool LIT, int KIND>
 __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a) {
   static_assert(PERC_RULE_BOND == PERC_BOND && PERC_RULE_SITE == PERC_SITE &&
@@ -44,14 +44,10 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Geom g = a.g;
   const int m = g.m, T = g.t, N = a.N;
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int t = threadIdx.x;
   const int item = blockIdx.x;
   // labeling view of the arena
-  int* parent = reinterpret_cast<int*>(smem);
-  uint8_t* bocc = reinterpret_cast<uint8_t*>(smem + a.L.oBocc);
-  uint8_t* member = reinterpret_cast<uint8_t*>(smem + a.L.oMem);
-  uint8_t* flag = reinterpret_cast<uint8_t*>(smem + a.L.oFlag);
-  uint8_t* socc = KIND != PERC_BOND ? reinterpret_cast<uint8_t*>(smem + a.L.oSocc) : nullptr;
+  const LabelArrays lv = label_arrays<KIND>(smem, a.L.oBocc, a.L.oMem, a.L.oFlag, a.L.oSocc);
   // solver view
   double* s_p = reinterpret_cast<double*>(smem);
   double* s_x = reinterpret_cast<double*>(smem + a.L.oX);    // rows 0..m-1, then N-m..N-1
@@ -63,100 +59,10 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
   uint16_t* s_cur = reinterpret_cast<uint16_t*>(smem + a.L.oCur);
   int* s_i = reinterpret_cast<int*>(smem + a.L.oInt);
 
-  const int trial = a.item_trial[item];
-  const int count = KIND != PERC_SITE ? a.item_count[item] : 0;
-  const int nsite = KIND != PERC_BOND ? a.item_nsites[item] : 0;
-  const int* __restrict__ rank = KIND != PERC_SITE ? a.rank + (size_t)trial * a.nb : nullptr;
-  const int* __restrict__ rank_s = KIND != PERC_BOND ? a.rank_s + (size_t)trial * T : nullptr;
-  BatchOut* out = a.out + item;
-
-  // ---- occupancy (k_batch_cond's statements)
-  {
-    const int nw = (int)(sizeof(StencilForms) / 4);
-    const int* src = reinterpret_cast<const int*>(a.forms);
-    int* dst = reinterpret_cast<int*>(sF);
-    for (int k = t; k < nw; k += NT) dst[k] = src[k];
-  }
-  if (t < 8) s_i[t] = t == 2 ? INT_MAX : 0;
-  for (int s = t; s <= T; s += NT) {
-    parent[s] = s;
-    if constexpr (KIND == PERC_BOND) {
-      member[s] = 0;
-    } else {
-      const uint8_t o = s >= 1 && rank_s[s - 1] < nsite ? 1 : 0;
-      socc[s] = o;
-      member[s] = o;
-    }
-  }
-  for (int c = t; c <= m; c += NT) flag[c] = 0;
-  if constexpr (KIND == PERC_SITE) {
-    for (int id = t; id < a.nb; id += NT) bocc[id] = 0;
-  } else {
-    for (int id = t; id < a.nb; id += NT) bocc[id] = rank[id] < count ? 1 : 0;
-  }
-  load_forms(*a.forms, s_off);  // (ends with a workgroup barrier)
-
-  // ---- labeling
-  lds_label<NT>(g, a.bond_first, parent, [&](int pass, int s, int, int q, int id) {
-    if constexpr (KIND == PERC_BOND) {
-      if (!bocc[id]) return false;
-      if (pass == 0) {
-        member[s] = 1;
-        member[q] = 1;
-      }
-      return true;
-    } else if constexpr (KIND == PERC_SITE) {
-      return socc[s] && socc[q];
-    } else {
-      return bocc[id] && socc[s] && socc[q];
-    }
-  });
-
-  // ---- spanning (k_span_top's rule): root <= m and a top-row member
-  for (int c = t; c < m; c += NT) {
-    const int s = T - m + 1 + c;
-    if (member[s] && parent[s] <= m) flag[parent[s]] = 1;
-  }
-  __syncthreads();
-  {
-    int ncl = 0, nsp = 0, mn = INT_MAX;
-    for (int s = t + 1; s <= T; s += NT) ncl += parent[s] == s && member[s];
-    for (int c = t + 1; c <= m; c += NT)
-      if (flag[c]) {
-        ++nsp;
-        mn = min(mn, c);
-      }
-    if (ncl) atomicAdd(&s_i[0], ncl);
-    if (nsp) {
-      atomicAdd(&s_i[1], nsp);
-      atomicMin(&s_i[2], mn);
-    }
-  }
-  __syncthreads();
-  const int nclusters = s_i[0], nspan = s_i[1];
-  const int root = nspan > 0 ? s_i[2] : 0;
-  if (root) {
-    int cnt = 0;
-    for (int s = t + 1; s <= T; s += NT) cnt += member[s] && parent[s] == root;
-    if (cnt) atomicAdd(&s_i[3], cnt);
-  }
-  __syncthreads();
-  const int span_sites = s_i[3];
-  const bool stop = nspan != 1 || !a.solve;  // (uniform: LDS values after a barrier)
-  if (t == 0) {
-    out->nclusters = nclusters;
-    out->nspan = nspan;
-    out->span_root = root;
-    out->span_sites = span_sites;
-    out->fallback = nspan > 1 ? 1 : 0;  // the lowest-label rule: host replay
-    out->pad = 0;
-    if (stop) {
-      out->status = nspan == 0 ? 1 : 0;
-      out->iter = 0;
-      out->err = 0.0;
-    }
-  }
-  if (stop) return;
+  // ---- occupancy, labeling, spanning, the item's header (perc_batch_item.h)
+  const BatchFront front = batch_front<NT, KIND>(a, g, lv, sF, s_off, s_i);
+  if (front.stop) return;
+  const int root = front.root;
 
   // ---- assembly: the thread that owns row i assembles it; its code goes
   // into the thread's packed code registers and its rhs (zero below the top
@@ -172,7 +78,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
   for (int i = t; i < N; i += NT) {
     uint16_t c;
     double b;
-    assemble_row_vals<false>(g, i, a.bond_first, bocc, socc, parent, nullptr, nullptr, nullptr, &b,
+    assemble_row_vals<false>(g, i, a.bond_first, lv.bocc, lv.socc, lv.parent, nullptr, nullptr, nullptr, &b,
                              &c, a.sflag, *sF, a.fast, a.fl, a.fr, a.bf_closed, RULE, g0, leak, Va,
                              root, nullptr);
     const int j = i / NT;  // (uniform)
@@ -182,23 +88,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
 #pragma unroll
     for (int jj = 0; jj < kLargeEPT; ++jj) rv[jj] = jj == j ? b : rv[jj];
   }
-#pragma unroll 1
-  for (int idx = t; idx < 2 * m; idx += NT) {
-    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
-    const int ps = parent[s];
-    int nbr[6];
-    const int cnt = sorted_neighbours(g, s, nbr);
-    unsigned cc = 0;
-    for (int j = 0; j < cnt; ++j) {
-      const int c = nbr[j];
-      const int id = s < c ? bond_id(g, a.bond_first, s, c) : bond_id(g, a.bond_first, c, s);
-      unsigned kind = 0;  // no bond: 0.0 (k_currents)
-      if (id >= 0)
-        kind = bond_value(RULE, id, s, c, ps, bocc, socc, root, g0, leak, nullptr) == -g0 ? 2u : 1u;
-      cc |= kind << (2 * j);
-    }
-    s_cur[idx] = (uint16_t)cc;
-  }
+  encode_electrode_rows<NT, RULE>(g, a.bond_first, lv, root, g0, leak, s_cur);
   __syncthreads();  // the labeling arrays are dead from here: p, x and the staging row take their place
 
   // ---- solve: k_cg_small<true, LIT>, the prologue included (x = 0, r = b)
@@ -231,69 +121,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
     }
     return st_combine<kMaxSlots>(c, xn, use, pi, ng0, nleak);
   };
-  // x += ak p on the rows the currents read (rows below m, rows from N - m)
-  auto x_add = [&](int i, double akp) {
-    if (i < m) s_x[i] = s_x[i] + akp;
-    if (i >= N - m) s_x[m + (i - (N - m))] = s_x[m + (i - (N - m))] + akp;
-  };
-#pragma unroll
-  for (int j = 0; j < kLargeEPT; ++j) {  // x = 0, by the row's owner
-    const int i = t + j * NT;
-    if (i < N) {
-      if (i < m) s_x[i] = 0.0;
-      if (i >= N - m) s_x[m + (i - (N - m))] = 0.0;
-    }
-  }
-  // workgroup sum: per-wave butterfly, then the waves in order
-  auto wg_sum = [&](double v0, double v1, double* o0, double* o1) {
-    v0 = wave_sum(v0);
-    v1 = wave_sum(v1);
-    if (lane == 0) {
-      s_red[wid] = v0;
-      s_red[16 + wid] = v1;
-    }
-    __syncthreads();
-    double t0 = s_red[0], t1 = s_red[16];
-    for (int w = 1; w < NT / 64; ++w) {
-      t0 = t0 + s_red[w];
-      t1 = t1 + s_red[16 + w];
-    }
-    __syncthreads();  // s_red reuse
-    *o0 = t0;
-    *o1 = t1;
-  };
-  // literal order, one round: every thread's row-j term(s) into the staging
-  // row (rows j NT .. j NT + NT - 1, ascending in t); wave 0 folds them into
-  // its accumulator, which it carries from round to round
-  auto lit_round2 = [&](int j, bool have, double t0, double t1, double (&acc)[2]) {
-    if (have) {
-      s_st[t] = t0;
-      s_st[NT + t] = t1;
-    }
-    __syncthreads();
-    if (wid == 0) {
-      const int cnt = min(NT, N - j * NT);
-      for (int c0 = 0; c0 < cnt; c0 += 64) {
-        const int l = min(c0 + lane, cnt - 1);
-        const double tz[2] = {s_st[l], s_st[NT + l]};
-        fold_chunk<2, 8>(tz, min(64, cnt - c0), acc);
-      }
-    }
-    __syncthreads();  // the staging row is free again
-  };
-  auto lit_round1 = [&](int j, bool have, double t0, double (&acc)[1]) {
-    if (have) s_st[t] = t0;
-    __syncthreads();
-    if (wid == 0) {
-      const int cnt = min(NT, N - j * NT);
-      for (int c0 = 0; c0 < cnt; c0 += 64) {
-        const int l = min(c0 + lane, cnt - 1);
-        const double tz[1] = {s_st[l]};
-        fold_chunk<1, 8>(tz, min(64, cnt - c0), acc);
-      }
-    }
-    __syncthreads();
-  };
+  x_clear<NT, kLargeEPT>(s_x, m, N);  // x = 0, by the row's owner
   const int itol = a.itol, itmax = a.itmax;
   const double tol = a.tol;
   double bnrm, bknum;
@@ -305,7 +133,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
       const double rj = r_sel(j);
       const double dj = i < N ? code_diag(code_sel(j), ng0, nleak) : 1.0;
       const double zb = itol == 1 ? rj : rj / dj, z = rj / dj;
-      lit_round2(j, i < N, zb * zb, z * rj, acc);
+      lit_round<2, NT>(s_st, N, j, i < N, {zb * zb, z * rj}, acc);
     }
     if (t == 0) {
       s_red[32] = sqrt(acc[0]);
@@ -328,7 +156,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
       }
     }
     double tb, tz;
-    wg_sum(b2, zr0, &tb, &tz);
+    wg_sum2<NT>(s_red, b2, zr0, &tb, &tz);
     bnrm = sqrt(tb);
     bknum = tz;
   }
@@ -372,7 +200,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
           const double pi = s_p[i];
           tq = row_q(i, code_sel(j), pi) * pi;  // akden, bondc.f:803-805
         }
-        lit_round1(j, i < N, tq, acc);
+        lit_round<1, NT>(s_st, N, j, i < N, {tq}, acc);
       }
       if (t == 0) s_red[32] = acc[0];
       __syncthreads();
@@ -391,7 +219,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
           dot = dot + q * pi;
         }
       }
-      wg_sum(dot, 0.0, &akden, &unused);
+      wg_sum2<NT>(s_red, dot, 0.0, &akden, &unused);
     }
     ak = bknum / akden;
     // pass 2: q held (fast order) or formed again by the same call on the
@@ -408,7 +236,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
           const unsigned c = code_sel(j);
           const double pi = s_p[i];
           const double q = row_q(i, c, pi);
-          x_add(i, ak * pi);
+          x_add(s_x, m, N, i, ak * pi);
           const double rn = r_sel(j) - ak * q;
 #pragma unroll
           for (int jj = 0; jj < kLargeEPT; ++jj) rv[jj] = jj == j ? rn : rv[jj];
@@ -416,7 +244,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
           t0 = zj * rn;  // bknum :785-787
           t1 = rn * rn;  // snrm :872-875
         }
-        lit_round2(j, i < N, t0, t1, acc);
+        lit_round<2, NT>(s_st, N, j, i < N, {t0, t1}, acc);
       }
       if (t == 0) {
         s_red[32] = acc[0];
@@ -438,7 +266,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
           double q;
           if constexpr (kHoldQ) q = qv[j];
           else q = row_q(i, c, pi);
-          x_add(i, ak * pi);
+          x_add(s_x, m, N, i, ak * pi);
           const double rn = rv[j] - ak * q;
           rv[j] = rn;
           const double z = rn / code_diag(c, ng0, nleak);
@@ -446,7 +274,7 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
           rr = rr + rn * rn;
         }
       }
-      wg_sum(zr, rr, &tzr, &trr);
+      wg_sum2<NT>(s_red, zr, rr, &tzr, &trr);
     }
     err = sqrt(trr) / bnrm;
     bk = tzr / bknum;
@@ -458,69 +286,31 @@ __global__ __launch_bounds__(kLargeNT) void k_batch_cond_large(BatchLargeArgs a)
   // ---- currents: k_currents' expression of the current rule on the 2m
   // electrode sites; their interior neighbours are rows below m or from N - m
   __syncthreads();
-  auto xe = [&](int i) -> double { return i < m ? s_x[i] : s_x[m + (i - (N - m))]; };
   double* iout = a.iout + (size_t)item * 2 * m;
+  auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : x_at(s_x, m, N, c - m - 1)); };
 #pragma unroll 1
   for (int idx = t; idx < 2 * m; idx += NT) {
-    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
-    int nbr[6];
-    const int cnt = sorted_neighbours(g, s, nbr);
     const unsigned cc = s_cur[idx];
-    double gv[6];
-    double rowsum = 0.0;
-    for (int j = 0; j < cnt; ++j) {
-      const unsigned kind = (cc >> (2 * j)) & 3u;
-      gv[j] = kind == 0 ? 0.0 : (kind == 2 ? -g0 : -leak);
-      rowsum = rowsum + gv[j];
-    }
-    const double d = -rowsum;
-    auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : xe(c - m - 1)); };
-    double acc;
-    if (a.cur_rule == PERC_CUR_FORTRAN) {
-      acc = d * V(s);
-      for (int j = 0; j < cnt; ++j)
-        if (fabs(gv[j]) >= 1.0e-10) acc = acc + gv[j] * V(nbr[j]);
-    } else {  // no threshold, the diagonal term before the first neighbour > s
-      acc = 0.0;
-      bool done = false;
-      for (int j = 0; j < cnt; ++j) {
-        if (!done && nbr[j] > s) {
-          acc = acc + d * V(s);
-          done = true;
-        }
-        acc = acc + gv[j] * V(nbr[j]);
-      }
-      if (!done) acc = acc + d * V(s);
-    }
-    iout[idx] = acc;
+    iout[idx] = electrode_current(
+        g, electrode_site(g, idx), a.cur_rule,
+        [&](int j) -> double { return electrode_code_value(cc, j, g0, leak); }, V);
   }
   if (t == 0) {
+    BatchOut* out = a.out + item;
     out->status = 0;
     out->iter = k;
     out->err = err;
   }
 }
 
-template <bool LIT, int KIND>
-hipError_t launch(perc_ctx* h, const BatchLargeArgs& a, int nitems) {
-  if (h->large_lds[LIT][KIND] < a.L.total) {  // dynamic LDS beyond the default limit
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_cond_large<LIT, KIND>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
-    h->large_lds[LIT][KIND] = a.L.total;
-  }
-  k_batch_cond_large<LIT, KIND><<<nitems, kLargeNT, a.L.total, h->stream>>>(a);
-  return dbg_sync(h->stream, "k_batch_cond_large");
-}
-
 }  // namespace
 
-hipError_t dev_batch_large_launch(perc_ctx* h, int kind, bool literal, BatchLargeArgs a, int nitems) {
-  a.L = batch_large_lds(h->g, kind);
-  if (kind == PERC_BOND)
-    return literal ? launch<true, PERC_BOND>(h, a, nitems) : launch<false, PERC_BOND>(h, a, nitems);
-  if (kind == PERC_SITE)
-    return literal ? launch<true, PERC_SITE>(h, a, nitems) : launch<false, PERC_SITE>(h, a, nitems);
-  return literal ? launch<true, PERC_SITEBOND>(h, a, nitems) : launch<false, PERC_SITEBOND>(h, a, nitems);
+hipError_t dev_batch_large_launch(perc_ctx* h, int kind, bool literal, const BatchItemArgs& c, int nitems) {
+  const BatchLargeArgs a{c, batch_large_lds(h->g, kind)};
+  return dispatch_kind_order(kind, literal, [&](auto lit, auto kd) {
+    return launch_lds(&k_batch_cond_large<lit(), kd()>, &h->large_lds[lit()][kd()], a, nitems, kLargeNT,
+                      h->stream, "k_batch_cond_large");
+  });
 }
 
 }  // namespace perc

@@ -178,37 +178,19 @@ struct ScanState {
   int lds_attr[3][3] = {};  // dynamic LDS granted per instantiation
 };
 
-template <int NT, int KIND>
-hipError_t launch(ScanState* S, int slot, const ScanArgs& a, int ntrials, hipStream_t st) {
-  if (S->lds_attr[slot][KIND] < a.L.total) {  // dynamic LDS beyond the default limit
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_scan<NT, KIND>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
-    S->lds_attr[slot][KIND] = a.L.total;
-  }
-  k_batch_scan<NT, KIND><<<ntrials, NT, a.L.total, st>>>(a);
-  return dbg_sync(st, "k_batch_scan");
-}
-
 template <int NT>
 hipError_t launch_kind(ScanState* S, int slot, int kind, const ScanArgs& a, int ntrials, hipStream_t st) {
-  if (kind == PERC_BOND) return launch<NT, PERC_BOND>(S, slot, a, ntrials, st);
-  if (kind == PERC_SITE) return launch<NT, PERC_SITE>(S, slot, a, ntrials, st);
-  return launch<NT, PERC_SITEBOND>(S, slot, a, ntrials, st);
+  auto launch = [&](auto kd) {
+    return launch_lds(&k_batch_scan<NT, kd()>, &S->lds_attr[slot][kd()], a, ntrials, NT, st, "k_batch_scan");
+  };
+  if (kind == PERC_BOND) return launch(std::integral_constant<int, PERC_BOND>{});
+  if (kind == PERC_SITE) return launch(std::integral_constant<int, PERC_SITE>{});
+  return launch(std::integral_constant<int, PERC_SITEBOND>{});
 }
 
 ScanState* scan_state(perc_ctx* h) {
   if (!h->scan) h->scan = new ScanState();
   return static_cast<ScanState*>(h->scan);
-}
-
-hipError_t grow(int** p, size_t* cap, size_t n) {
-  if (*cap >= n) return hipSuccess;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(dmalloc(p, n));
-  *cap = n;
-  return hipSuccess;
 }
 
 }  // namespace
@@ -229,14 +211,11 @@ hipError_t dev_scan_run(perc_ctx* h, int kind, int scan, int ntrials, const int*
   if (ntrials == 0) return hipSuccess;
   ScanState* S = scan_state(h);
   hipStream_t st = h->stream;
-  if (S->trial_cap < (size_t)ntrials) {
-    if (S->d_fixed) HIP_TRY(hipFree(S->d_fixed));
-    if (S->d_out) HIP_TRY(hipFree(S->d_out));
-    S->d_fixed = nullptr;
-    S->d_out = nullptr;
+  if (S->trial_cap < (size_t)ntrials) {  // d_fixed and d_out share one capacity
+    size_t cf = 0, co = 0;  // zero on purpose: grow() frees and allocates both afresh
     S->trial_cap = 0;
-    HIP_TRY(dmalloc(&S->d_fixed, (size_t)ntrials));
-    HIP_TRY(dmalloc(&S->d_out, (size_t)ntrials));
+    HIP_TRY(grow(&S->d_fixed, &cf, (size_t)ntrials));
+    HIP_TRY(grow(&S->d_out, &co, (size_t)ntrials));
     S->trial_cap = ntrials;
   }
   if (kind == PERC_SITEBOND)

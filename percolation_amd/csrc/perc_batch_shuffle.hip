@@ -119,27 +119,6 @@ struct ShuffleState {
   int lds_attr[2] = {};  // dynamic LDS granted per instantiation
 };
 
-hipError_t grow(int** p, size_t* cap, size_t n) {
-  if (*cap >= n) return hipSuccess;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(dmalloc(p, n));
-  *cap = n;
-  return hipSuccess;
-}
-
-template <bool JUMP>
-hipError_t launch(ShuffleState* S, const ShuffleArgs& a, int ntrials, hipStream_t st) {
-  if (S->lds_attr[JUMP] < a.L.total) {  // dynamic LDS beyond the default limit
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shuffle_ranks<JUMP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
-    S->lds_attr[JUMP] = a.L.total;
-  }
-  k_shuffle_ranks<JUMP><<<ntrials, 64, a.L.total, st>>>(a);
-  return dbg_sync(st, "k_shuffle_ranks");
-}
-
 }  // namespace
 
 void dev_shuffle_free(perc_ctx* h) {
@@ -178,8 +157,9 @@ hipError_t dev_shuffle_run(perc_ctx* h, int list, int ntrials, const int* seeds,
   a.L = shuffle_lds(N);
   // PERC_SHUFFLE_FORM=plain: lane 0 alone (the A/B of tools/scan_bench.py)
   const char* form = std::getenv("PERC_SHUFFLE_FORM");
-  if (form && !std::strcmp(form, "plain")) HIP_TRY(launch<false>(S, a, ntrials, st));
-  else HIP_TRY(launch<true>(S, a, ntrials, st));
+  if (form && !std::strcmp(form, "plain"))
+    HIP_TRY(launch_lds(&k_shuffle_ranks<false>, &S->lds_attr[0], a, ntrials, 64, st, "k_shuffle_ranks"));
+  else HIP_TRY(launch_lds(&k_shuffle_ranks<true>, &S->lds_attr[1], a, ntrials, 64, st, "k_shuffle_ranks"));
   if (nord) HIP_TRY(hipMemcpyAsync(orders_out, S->d_orders, sizeof(int) * nord, hipMemcpyDeviceToHost, st));
   if (ranks_out)
     HIP_TRY(hipMemcpyAsync(ranks_out, d_rank, sizeof(int) * (size_t)ntrials * (size_t)N,

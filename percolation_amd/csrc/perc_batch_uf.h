@@ -1,5 +1,6 @@
 // perc_batch_uf.h -- the in-LDS union-find the one-workgroup kernels share
-// (perc_batch.hip: k_batch_cond; perc_batch_scan.hip: k_batch_scan): the
+// (perc_batch_item.h: the conductance kernels' batch_front;
+// perc_batch_scan.hip: k_batch_scan): the
 // root walk and the hook / flatten passes over a bond predicate.
 #pragma once
 #include "perc_common.h"

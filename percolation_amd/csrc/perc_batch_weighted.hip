@@ -2,22 +2,23 @@
 // multipliers (ConductCalc.m condtype 2, perc_batch_cond_weighted).
 // k_twister_stream: MT19937 streams on the device, one wave per seed, bit for
 // bit perc_twister_uniform.  k_batch_cond_w: k_batch_cond_large's
-// one-workgroup realisation (occupancy from ranks, union-find labeling in
-// LDS, the spanning rule, assemble_row_vals, the CG loop in both dot orders,
-// the currents) with the rows' slot values themselves in LDS where the other
+// one-workgroup realisation (perc_batch_item.h's front end, sums and currents
+// around this file's weights, assembly and CG loop in both dot orders) with
+// the rows' slot values themselves in LDS where the other
 // two kernels rebuild them from a two-value code: G = -g0 w[id] takes as
 // many values as there are bonds.  The operator is the CSR one of the single
 // path's weighted solve (dsprsax order: the diagonal, then the used slots in
 // slot order), so the literal order is bitwise perc_set_bond_weights +
 // perc_conductance under PERC_DOT_LITERAL.
-#include <climits>
-
-#include "perc_asm_row.h"
-#include "perc_batch.h"
-#include "perc_batch_uf.h"
+#include "perc_batch_item.h"
 
 namespace perc {
 namespace {
+
+struct BatchWArgs : BatchItemArgs {
+  BatchWLds L;
+  BatchWItems w;  // (after the plan: see profiles/batch_front_isa_compare.txt)
+};
 
 // ---------------------------------------------------------------------------
 // MT19937 (Matsumoto & Nishimura), perc_host.cpp's Twister on one wave: the
@@ -107,11 +108,9 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int item = blockIdx.x;
   // labeling view of the arena
-  int* parent = reinterpret_cast<int*>(smem);
-  uint8_t* bocc = reinterpret_cast<uint8_t*>(smem + a.L.oBocc);
-  uint8_t* member = reinterpret_cast<uint8_t*>(smem + a.L.oMem);
-  uint8_t* flag = reinterpret_cast<uint8_t*>(smem + a.L.oFlag);
-  uint8_t* socc = KIND != PERC_BOND ? reinterpret_cast<uint8_t*>(smem + a.L.oSocc) : nullptr;
+  const LabelArrays lv = label_arrays<KIND>(smem, a.L.oBocc, a.L.oMem, a.L.oFlag, a.L.oSocc);
+  int* parent = lv.parent;
+  uint8_t *bocc = lv.bocc, *socc = lv.socc;
   // solver view
   double* s_p = reinterpret_cast<double*>(smem);
   double* s_x = reinterpret_cast<double*>(smem + a.L.oX);       // rows 0..m-1, then N-m..N-1
@@ -124,100 +123,10 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
   StencilForms* sF = reinterpret_cast<StencilForms*>(smem + a.L.oF);
   int* s_i = reinterpret_cast<int*>(smem + a.L.oInt);  // 8 counters, 16 wave totals
 
-  const int trial = a.item_trial[item];
-  const int count = KIND != PERC_SITE ? a.item_count[item] : 0;
-  const int nsite = KIND != PERC_BOND ? a.item_nsites[item] : 0;
-  const int* __restrict__ rank = KIND != PERC_SITE ? a.rank + (size_t)trial * a.nb : nullptr;
-  const int* __restrict__ rank_s = KIND != PERC_BOND ? a.rank_s + (size_t)trial * T : nullptr;
-  BatchOut* out = a.out + item;
-
-  // ---- occupancy (k_batch_cond's statements)
-  {
-    const int nw = (int)(sizeof(StencilForms) / 4);
-    const int* src = reinterpret_cast<const int*>(a.forms);
-    int* dst = reinterpret_cast<int*>(sF);
-    for (int k = t; k < nw; k += NT) dst[k] = src[k];
-  }
-  if (t < 8) s_i[t] = t == 2 ? INT_MAX : 0;
-  for (int s = t; s <= T; s += NT) {
-    parent[s] = s;
-    if constexpr (KIND == PERC_BOND) {
-      member[s] = 0;
-    } else {
-      const uint8_t o = s >= 1 && rank_s[s - 1] < nsite ? 1 : 0;
-      socc[s] = o;
-      member[s] = o;
-    }
-  }
-  for (int c = t; c <= m; c += NT) flag[c] = 0;
-  if constexpr (KIND == PERC_SITE) {
-    for (int id = t; id < a.nb; id += NT) bocc[id] = 0;
-  } else {
-    for (int id = t; id < a.nb; id += NT) bocc[id] = rank[id] < count ? 1 : 0;
-  }
-  load_forms(*a.forms, s_off);  // (ends with a workgroup barrier)
-
-  // ---- labeling
-  lds_label<NT>(g, a.bond_first, parent, [&](int pass, int s, int, int q, int id) {
-    if constexpr (KIND == PERC_BOND) {
-      if (!bocc[id]) return false;
-      if (pass == 0) {
-        member[s] = 1;
-        member[q] = 1;
-      }
-      return true;
-    } else if constexpr (KIND == PERC_SITE) {
-      return socc[s] && socc[q];
-    } else {
-      return bocc[id] && socc[s] && socc[q];
-    }
-  });
-
-  // ---- spanning (k_span_top's rule): root <= m and a top-row member
-  for (int c = t; c < m; c += NT) {
-    const int s = T - m + 1 + c;
-    if (member[s] && parent[s] <= m) flag[parent[s]] = 1;
-  }
-  __syncthreads();
-  {
-    int ncl = 0, nsp = 0, mn = INT_MAX;
-    for (int s = t + 1; s <= T; s += NT) ncl += parent[s] == s && member[s];
-    for (int c = t + 1; c <= m; c += NT)
-      if (flag[c]) {
-        ++nsp;
-        mn = min(mn, c);
-      }
-    if (ncl) atomicAdd(&s_i[0], ncl);
-    if (nsp) {
-      atomicAdd(&s_i[1], nsp);
-      atomicMin(&s_i[2], mn);
-    }
-  }
-  __syncthreads();
-  const int nclusters = s_i[0], nspan = s_i[1];
-  const int root = nspan > 0 ? s_i[2] : 0;
-  if (root) {
-    int cnt = 0;
-    for (int s = t + 1; s <= T; s += NT) cnt += member[s] && parent[s] == root;
-    if (cnt) atomicAdd(&s_i[3], cnt);
-  }
-  __syncthreads();
-  const int span_sites = s_i[3];
-  const bool stop = nspan != 1 || !a.solve;  // (uniform: LDS values after a barrier)
-  if (t == 0) {
-    out->nclusters = nclusters;
-    out->nspan = nspan;
-    out->span_root = root;
-    out->span_sites = span_sites;
-    out->fallback = nspan > 1 ? 1 : 0;  // the lowest-label rule: host replay
-    out->pad = 0;
-    if (stop) {
-      out->status = nspan == 0 ? 1 : 0;
-      out->iter = 0;
-      out->err = 0.0;
-    }
-  }
-  if (stop) return;
+  // ---- occupancy, labeling, spanning, the item's header (perc_batch_item.h)
+  const BatchFront front = batch_front<NT, KIND>(a, g, lv, sF, s_off, s_i);
+  if (front.stop) return;
+  const int root = front.root;
 
   // ---- weights by bond id.  Explicit: the item's row.  ConductCalc: one
   // draw per bond the rule gives -g0 (k_bond_mask's predicate), in bond-list
@@ -227,11 +136,11 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
   // draws; the others get 1.0.  The row goes to the launch's scratch and is
   // read back like an explicit one after the barrier.
   const double* w;
-  if (a.item_wset) {
-    w = a.wrows + (size_t)a.item_wset[item] * a.nb;
+  if (a.w.item_wset) {
+    w = a.w.wrows + (size_t)a.w.item_wset[item] * a.nb;
   } else {
-    double* wr = a.wscratch + (size_t)item * a.wstride;
-    const double* __restrict__ u = a.u + (size_t)item * a.nb;
+    double* wr = a.w.wscratch + (size_t)item * a.w.wstride;
+    const double* __restrict__ u = a.w.u + (size_t)item * a.nb;
     const int per = (T - 1 + NT - 1) / NT;
     const int s0 = 1 + t * per, s1 = min(T, s0 + per);  // sites s0 .. s1 - 1 of 1 .. T - 1
     auto walk = [&](auto&& f) {
@@ -306,7 +215,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
   }
 #pragma unroll 1
   for (int idx = t; idx < 2 * m; idx += NT) {
-    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
+    const int s = electrode_site(g, idx);
     const int ps = parent[s];
     int nbr[6];
     const int cnt = sorted_neighbours(g, s, nbr);
@@ -340,69 +249,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
     }
     return acc;
   };
-  // x += ak p on the rows the currents read (rows below m, rows from N - m)
-  auto x_add = [&](int i, double akp) {
-    if (i < m) s_x[i] = s_x[i] + akp;
-    if (i >= N - m) s_x[m + (i - (N - m))] = s_x[m + (i - (N - m))] + akp;
-  };
-#pragma unroll
-  for (int j = 0; j < EPT; ++j) {  // x = 0, by the row's owner
-    const int i = t + j * NT;
-    if (i < N) {
-      if (i < m) s_x[i] = 0.0;
-      if (i >= N - m) s_x[m + (i - (N - m))] = 0.0;
-    }
-  }
-  // workgroup sum: per-wave butterfly, then the waves in order
-  auto wg_sum = [&](double v0, double v1, double* o0, double* o1) {
-    v0 = wave_sum(v0);
-    v1 = wave_sum(v1);
-    if (lane == 0) {
-      s_red[wid] = v0;
-      s_red[16 + wid] = v1;
-    }
-    __syncthreads();
-    double t0 = s_red[0], t1 = s_red[16];
-    for (int w2 = 1; w2 < NT / 64; ++w2) {
-      t0 = t0 + s_red[w2];
-      t1 = t1 + s_red[16 + w2];
-    }
-    __syncthreads();  // s_red reuse
-    *o0 = t0;
-    *o1 = t1;
-  };
-  // literal order, one round: every thread's row-j term(s) into the staging
-  // row (rows j NT .. j NT + NT - 1, ascending in t); wave 0 folds them into
-  // its accumulator, which it carries from round to round
-  auto lit_round2 = [&](int j, bool have, double t0, double t1, double (&acc)[2]) {
-    if (have) {
-      s_st[t] = t0;
-      s_st[NT + t] = t1;
-    }
-    __syncthreads();
-    if (wid == 0) {
-      const int cnt = min(NT, N - j * NT);
-      for (int c0 = 0; c0 < cnt; c0 += 64) {
-        const int l = min(c0 + lane, cnt - 1);
-        const double tz[2] = {s_st[l], s_st[NT + l]};
-        fold_chunk<2, 8>(tz, min(64, cnt - c0), acc);
-      }
-    }
-    __syncthreads();  // the staging row is free again
-  };
-  auto lit_round1 = [&](int j, bool have, double t0, double (&acc)[1]) {
-    if (have) s_st[t] = t0;
-    __syncthreads();
-    if (wid == 0) {
-      const int cnt = min(NT, N - j * NT);
-      for (int c0 = 0; c0 < cnt; c0 += 64) {
-        const int l = min(c0 + lane, cnt - 1);
-        const double tz[1] = {s_st[l]};
-        fold_chunk<1, 8>(tz, min(64, cnt - c0), acc);
-      }
-    }
-    __syncthreads();
-  };
+  x_clear<NT, EPT>(s_x, m, N);  // x = 0, by the row's owner
   const int itol = a.itol, itmax = a.itmax;
   const double tol = a.tol;
   double bnrm, bknum;
@@ -413,7 +260,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
       if (j * NT < N) {  // (uniform)
         const int i = t + j * NT;
         const double zb = itol == 1 ? rv[j] : rv[j] / dv[j], z = rv[j] / dv[j];
-        lit_round2(j, i < N, zb * zb, z * rv[j], acc);
+        lit_round<2, NT>(s_st, N, j, i < N, {zb * zb, z * rv[j]}, acc);
       }
     }
     if (t == 0) {
@@ -436,7 +283,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
       }
     }
     double tb, tz;
-    wg_sum(b2, zr0, &tb, &tz);
+    wg_sum2<NT>(s_red, b2, zr0, &tb, &tz);
     bnrm = sqrt(tb);
     bknum = tz;
   }
@@ -470,7 +317,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
             const double pi = s_p[i];
             tq = row_q(i, fc[j], dv[j], pi) * pi;  // akden, bondc.f:803-805
           }
-          lit_round1(j, i < N, tq, acc);
+          lit_round<1, NT>(s_st, N, j, i < N, {tq}, acc);
         }
       }
       if (t == 0) s_red[32] = acc[0];
@@ -489,7 +336,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
           dot = dot + q * pi;
         }
       }
-      wg_sum(dot, 0.0, &akden, &unused);
+      wg_sum2<NT>(s_red, dot, 0.0, &akden, &unused);
     }
     ak = bknum / akden;
     // pass 2: q held (fast order) or formed again by the same call on the
@@ -506,14 +353,14 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
           if (i < N) {
             const double pi = s_p[i];
             const double q = row_q(i, fc[j], dv[j], pi);
-            x_add(i, ak * pi);
+            x_add(s_x, m, N, i, ak * pi);
             const double rn = rv[j] - ak * q;
             rv[j] = rn;
             const double zj = rn / dv[j];
             t0 = zj * rn;  // bknum :785-787
             t1 = rn * rn;  // snrm :872-875
           }
-          lit_round2(j, i < N, t0, t1, acc);
+          lit_round<2, NT>(s_st, N, j, i < N, {t0, t1}, acc);
         }
       }
       if (t == 0) {
@@ -531,7 +378,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
         const int i = t + j * NT;
         if (i < N) {
           const double pi = s_p[i];
-          x_add(i, ak * pi);
+          x_add(s_x, m, N, i, ak * pi);
           const double rn = rv[j] - ak * qv[j];
           rv[j] = rn;
           const double z = rn / dv[j];
@@ -539,7 +386,7 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
           rr = rr + rn * rn;
         }
       }
-      wg_sum(zr, rr, &tzr, &trr);
+      wg_sum2<NT>(s_red, zr, rr, &tzr, &trr);
     }
     err = sqrt(trr) / bnrm;
     bk = tzr / bknum;
@@ -552,76 +399,31 @@ __global__ __launch_bounds__(NT) void k_batch_cond_w(BatchWArgs a) {
   // electrode sites, on the stored slot values; their interior neighbours are
   // rows below m or from N - m
   __syncthreads();
-  auto xe = [&](int i) -> double { return i < m ? s_x[i] : s_x[m + (i - (N - m))]; };
   double* iout = a.iout + (size_t)item * 2 * m;
+  auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : x_at(s_x, m, N, c - m - 1)); };
 #pragma unroll 1
-  for (int idx = t; idx < 2 * m; idx += NT) {
-    const int s = idx < m ? idx + 1 : T - m + 1 + (idx - m);
-    int nbr[6];
-    const int cnt = sorted_neighbours(g, s, nbr);
-    double rowsum = 0.0;
-    for (int j = 0; j < cnt; ++j) rowsum = rowsum + s_el[idx * 6 + j];
-    const double d = -rowsum;
-    auto V = [&](int c) -> double { return c <= m ? 0.0 : (c > T - m ? Va : xe(c - m - 1)); };
-    double acc;
-    if (a.cur_rule == PERC_CUR_FORTRAN) {
-      acc = d * V(s);
-      for (int j = 0; j < cnt; ++j) {
-        const double gv = s_el[idx * 6 + j];
-        if (fabs(gv) >= 1.0e-10) acc = acc + gv * V(nbr[j]);
-      }
-    } else {  // no threshold, the diagonal term before the first neighbour > s
-      acc = 0.0;
-      bool done = false;
-      for (int j = 0; j < cnt; ++j) {
-        if (!done && nbr[j] > s) {
-          acc = acc + d * V(s);
-          done = true;
-        }
-        acc = acc + s_el[idx * 6 + j] * V(nbr[j]);
-      }
-      if (!done) acc = acc + d * V(s);
-    }
-    iout[idx] = acc;
-  }
+  for (int idx = t; idx < 2 * m; idx += NT)
+    iout[idx] = electrode_current(
+        g, electrode_site(g, idx), a.cur_rule, [&](int j) -> double { return s_el[idx * 6 + j]; }, V);
   if (t == 0) {
+    BatchOut* out = a.out + item;
     out->status = 0;
     out->iter = k;
     out->err = err;
   }
 }
 
-template <int NT, bool LIT, int KIND>
-hipError_t launch(perc_ctx* h, int slot, const BatchWArgs& a, int nitems) {
-  if (h->w_lds[slot][LIT][KIND] < a.L.total) {  // dynamic LDS beyond the default limit
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_cond_w<NT, LIT, KIND>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.L.total));
-    h->w_lds[slot][LIT][KIND] = a.L.total;
-  }
-  k_batch_cond_w<NT, LIT, KIND><<<nitems, NT, a.L.total, h->stream>>>(a);
-  return dbg_sync(h->stream, "k_batch_cond_w");
-}
-
-template <int NT>
-hipError_t launch_kind(perc_ctx* h, int slot, int kind, bool literal, const BatchWArgs& a, int nitems) {
-  if (kind == PERC_BOND)
-    return literal ? launch<NT, true, PERC_BOND>(h, slot, a, nitems)
-                   : launch<NT, false, PERC_BOND>(h, slot, a, nitems);
-  if (kind == PERC_SITE)
-    return literal ? launch<NT, true, PERC_SITE>(h, slot, a, nitems)
-                   : launch<NT, false, PERC_SITE>(h, slot, a, nitems);
-  return literal ? launch<NT, true, PERC_SITEBOND>(h, slot, a, nitems)
-                 : launch<NT, false, PERC_SITEBOND>(h, slot, a, nitems);
-}
-
 }  // namespace
 
-hipError_t dev_batch_w_launch(perc_ctx* h, int kind, bool literal, BatchWArgs a, int nitems) {
-  a.L = batch_w_lds(h->g, kind);
-  const int nt = batch_w_threads(h->N);
-  if (nt == 256) return launch_kind<256>(h, 0, kind, literal, a, nitems);
-  if (nt == 512) return launch_kind<512>(h, 1, kind, literal, a, nitems);
-  return launch_kind<1024>(h, 2, kind, literal, a, nitems);
+hipError_t dev_batch_w_launch(perc_ctx* h, int kind, bool literal, const BatchItemArgs& c,
+                              const BatchWItems& w, int nitems) {
+  const BatchWArgs a{c, batch_w_lds(h->g, kind), w};
+  return dispatch_threads(batch_w_threads(h->N), [&](auto nt, int slot) {
+    return dispatch_kind_order(kind, literal, [&](auto lit, auto kd) {
+      return launch_lds(&k_batch_cond_w<nt(), lit(), kd()>, &h->w_lds[slot][lit()][kd()], a, nitems, nt(),
+                        h->stream, "k_batch_cond_w");
+    });
+  });
 }
 
 hipError_t dev_twister_launch(perc_ctx* h, int nseeds, const unsigned* d_seeds, long long n, double* d_out) {

@@ -396,6 +396,33 @@ hipError_t dmalloc(T** p, size_t n) {
   return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (n ? n : 1));
 }
 
+// *p grown to n elements (capacity *cap); the contents are not kept
+template <typename T>
+hipError_t grow(T** p, size_t* cap, size_t n) {
+  if (*cap >= n) return hipSuccess;
+  if (*p) HIP_TRY(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(dmalloc(p, n));
+  *cap = n;
+  return hipSuccess;
+}
+
+// One launch of nblocks workgroups of nt threads of a kernel whose arena is
+// a.L.total bytes of dynamic LDS, beyond the default limit: *granted is what
+// this instantiation has been granted so far
+template <class Args>
+hipError_t launch_lds(void (*kern)(Args), int* granted, const Args& a, int nblocks, int nt, hipStream_t st,
+                      const char* name) {
+  if (*granted < a.L.total) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                a.L.total));
+    *granted = a.L.total;
+  }
+  kern<<<nblocks, nt, a.L.total, st>>>(a);
+  return dbg_sync(st, name);
+}
+
 hipError_t exclusive_scan(const int* in, int* out, int n, hipStream_t st) {
   const int nt = cdiv(n, kScanItems);
   int* totals = nullptr;

@@ -873,6 +873,70 @@ int perc_batch_cond_seeded(perc_ctx *h, int kind, int rule, int cur_rule, int nt
                            int solve, double Va, double g0, double leak, int itol,
                            double tol, int itmax, perc_batch_item *out);
 
+/* ---- batch of cluster tables (one workgroup per item) ----------------- *
+ * Every reference program writes its cluster table c(label): cln, maxcn,
+ * maxcs and the size of every cluster.  perc_batch_clusters forms that table's
+ * statistics for many (trial, nsites, nbonds) items in one launch -- the
+ * items, orders, counts and NULL rules of perc_batch_cond (a count of t + 1 /
+ * nb + 1 is the whole order; the spill slot takes a position and is no
+ * element) -- with the labeling and the spanning rule of perc_batch_scan.
+ * The clusters are the programs' non-empty c(label) entries; the phantom
+ * label the spill slot opens (hazard H2) is none and is never counted:
+ *   PERC_BOND      a connected set of occupied bonds (a site with no occupied
+ *                  bond is in none); size = its bonds
+ *   PERC_SITE      a connected set of occupied sites over the lattice's
+ *                  bonds, an isolated occupied site too; size = its sites
+ *   PERC_SITEBOND  a component of occupied sites linked by occupied bonds
+ *                  whose end sites are both occupied; size = its sites plus
+ *                  every occupied bond with at least one end site in it
+ *                  (sitebond.f's count)
+ *   PERC_SITEBOND, lone bond: an occupied bond with both end sites empty;
+ *                  size 1, it never spans
+ * The sizes do not depend on the order of occupation.  Several clusters may
+ * span; there is no fallback item: the record sums over all of them.
+ * Histogram row i (nexact + 32 ints): hist[s - 1] = clusters of size s for
+ * 1 <= s <= nexact, hist[nexact + floor(log2 s)] for every cluster (the octave
+ * part is complete on its own).  hist may be NULL.  The call chunks itself so
+ * that one launch's rank arrays and its histogram rows each stay under 64 MB
+ * of device memory, and leaves the context's single-realisation state
+ * untouched.  nitems == 0 is PERC_OK.  PERC_EINVAL (text in perc_last_error),
+ * before any device call: a lattice / nexact perc_batch_clusters_supported
+ * refuses, a bad kind, ntrials or nitems < 0, a missing list that the kind
+ * reads, item_trial outside 0..ntrials-1, a count outside 0..t+1 / 0..nb+1;
+ * the seeded form: a list perc_shuffle_device_supported refuses. */
+typedef struct {
+  int nclusters;   /* clusters counted, lone bonds included */
+  int nlone;       /* mixed kind: lone bonds; else 0 (perc_label's nclusters = nclusters - nlone) */
+  int nspan;       /* spanning clusters */
+  int span_root;   /* smallest spanning root (min site id), 0 if none */
+  int span_size;   /* size of that cluster, 0 if none */
+  int maxcs;       /* largest size, 0 if no cluster */
+  long long s1, s2;            /* sum of s, sum of s^2 over all clusters */
+  long long span_s1, span_s2;  /* the same over the spanning clusters only */
+} perc_cluster_item;
+/* host-only: 1 when the cluster kernel can run this lattice with this exact
+   range: what perc_scan_supported accepts (m, n >= 3, m*n <= 16384 sites) and
+   0 <= nexact <= 1024 (the histogram row beside the scan's arena in the
+   workgroup's 160 KB of LDS). */
+int perc_batch_clusters_supported(int lattice, int m, int n, int pbc, int nexact);
+int perc_batch_clusters(perc_ctx *h, int kind, int ntrials,
+                        const int *site_orders /* ntrials x (t+1), NULL for PERC_BOND */,
+                        const int *bond_orders /* ntrials x (nb+1), NULL for PERC_SITE */,
+                        int nitems, const int *item_trial,
+                        const int *item_nsites /* NULL for PERC_BOND */,
+                        const int *item_nbonds /* NULL for PERC_SITE */,
+                        int nexact, perc_cluster_item *out,
+                        int *hist /* nitems x (nexact+32), or NULL */);
+/* the same with seed lists (one seed per trial) in place of the order lists,
+   the orders shuffled on the device into the batch rank buffers
+   (perc_batch_shuffle): the same records item for item */
+int perc_batch_clusters_seeded(perc_ctx *h, int kind, int ntrials,
+                               const int *site_seeds /* ntrials, NULL for PERC_BOND */,
+                               const int *bond_seeds /* ntrials, NULL for PERC_SITE */,
+                               int nitems, const int *item_trial, const int *item_nsites,
+                               const int *item_nbonds, int nexact, perc_cluster_item *out,
+                               int *hist);
+
 /* ---- ensemble statistics (bond_cond, config 4) ----------------------- */
 /* Accumulate stats for one pb point: {count, sum G, sum G^2, count spanning,
    sum iter} into acc[5*point..]. */

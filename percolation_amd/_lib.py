@@ -60,6 +60,19 @@ class ScanItem(C.Structure):
     _fields_ = [("first", C.c_int), ("maxcs", C.c_int), ("span_size", C.c_int), ("nspan", C.c_int)]
 
 
+class ClusterItem(C.Structure):
+    _fields_ = [("nclusters", C.c_int), ("nlone", C.c_int), ("nspan", C.c_int), ("span_root", C.c_int),
+                ("span_size", C.c_int), ("maxcs", C.c_int), ("s1", C.c_longlong), ("s2", C.c_longlong),
+                ("span_s1", C.c_longlong), ("span_s2", C.c_longlong)]
+
+
+# perc_cluster_item as a numpy record (Context.batch_clusters, api.cluster_stats_host)
+CLUSTER_DTYPE = np.dtype([("nclusters", np.int32), ("nlone", np.int32), ("nspan", np.int32),
+                          ("span_root", np.int32), ("span_size", np.int32), ("maxcs", np.int32),
+                          ("s1", np.int64), ("s2", np.int64), ("span_s1", np.int64), ("span_s2", np.int64)])
+assert CLUSTER_DTYPE.itemsize == C.sizeof(ClusterItem) == 56
+
+
 class DslabBufs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("part_out", "part_all", "edge_lo", "edge_hi",
                                           "ghost_lo", "ghost_hi")]
@@ -207,6 +220,11 @@ SIGNATURES = {
     "perc_batch_cond_seeded": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP,
                                          _VP, _VP, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                          C.c_double, C.c_int, _VP]),
+    "perc_batch_clusters_supported": (C.c_int, [C.c_int] * 5),
+    "perc_batch_clusters": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int, _VP,
+                                      _VP]),
+    "perc_batch_clusters_seeded": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int,
+                                             _VP, _VP]),
     "perc_ensemble_ctx": (C.c_void_p, [_VP, C.c_int]),
     "perc_ensemble_trials": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP]),
     "perc_ensemble_allreduce": (C.c_int, [_VP, _D, C.c_int]),

@@ -147,6 +147,87 @@ def shuffle_device_supported(N):
     return bool(L.lib().perc_shuffle_device_supported(int(N)))
 
 
+def batch_clusters_supported(lattice, m, n, pbc=0, nexact=0):
+    """perc_batch_clusters_supported (host-only): True when the cluster kernel
+    (Context.batch_clusters) can run this lattice with this exact range --
+    what scan_supported accepts, and 0 <= nexact <= 1024."""
+    return bool(L.lib().perc_batch_clusters_supported(lattice, m, n, pbc, int(nexact)))
+
+
+def _whole_prefix(order, count, N):
+    """(order, count) as replay_labels takes them: a count of N + 1 is the
+    whole order with the spill slot dropped"""
+    if order is None:
+        return None, 0
+    o = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+    count = int(count)
+    if count > N:
+        o = np.ascontiguousarray(o[:count][o[:count] != 0][:N])
+        count = len(o)
+    return o, count
+
+
+def cluster_stats_host(lattice, m, n, pbc, kind, site_order=None, nsites=0, bond_order=None, nbonds=0,
+                       nexact=0):
+    """The record and histogram row of Context.batch_clusters for one item, on
+    the host (no device): from replay_labels' label arrays -- a cluster's size
+    is the number of bonds and sites that carry its label (bonds for BOND,
+    sites for SITE, both for SITEBOND), never csize, so the phantom label of
+    the shuffle's spill slot (H2) does not enter; spanning from the labels of
+    the bottom and top rows (BOND: of the bonds with an end site there).
+    Returns (record, hist): a CLUSTER_DTYPE scalar and nexact + 32 int32."""
+    kind, nexact = int(kind), int(nexact)
+    if kind not in (L.BOND, L.SITE, L.SITEBOND):
+        raise ValueError("cluster_stats_host: kind BOND, SITE or SITEBOND")
+    if not 0 <= nexact <= 1024:
+        raise ValueError("cluster_stats_host: nexact outside 0..1024")
+    t = m * n
+    b1, b2 = bond_list(lattice, m, n, pbc)
+    nb = len(b1)
+    so, ns = _whole_prefix(site_order if kind != L.BOND else None, nsites, t)
+    bo, nbo = _whole_prefix(bond_order if kind != L.SITE else None, nbonds, nb)
+    r = replay_labels(lattice, m, n, pbc, kind, site_order=so, nsites=ns, bond_order=bo, nbond=nbo)
+    sl, bl = r["site_label"], r["bond_label"]
+    nlab = 1 + max(int(sl.max()) if sl is not None and len(sl) else 0,
+                   int(bl.max()) if bl is not None and len(bl) else 0)
+    nsite = np.bincount(sl, minlength=nlab) if sl is not None else np.zeros(nlab, np.int64)
+    nbond = np.bincount(bl, minlength=nlab) if bl is not None else np.zeros(nlab, np.int64)
+    size = (nsite + nbond).astype(np.int64)
+    size[0] = 0  # (label 0: not occupied)
+    # the member sites of a label: its sites (SITE, SITEBOND), its bonds' end sites (BOND)
+    minsite = np.full(nlab, t + 1, dtype=np.int64)
+    bot = np.zeros(nlab, dtype=bool)
+    top = np.zeros(nlab, dtype=bool)
+    if kind == L.BOND:
+        for end in (b1, b2):
+            np.minimum.at(minsite, bl, end)
+            bot[bl[end <= m]] = True
+            top[bl[end > t - m]] = True
+    else:
+        np.minimum.at(minsite, sl, np.arange(1, t + 1))
+        bot[sl[:m]] = True
+        top[sl[t - m:]] = True
+    labels = np.nonzero(size)[0]
+    span = labels[bot[labels] & top[labels]]
+    s = size[labels]
+    rec = np.zeros((), dtype=L.CLUSTER_DTYPE)
+    rec["nclusters"] = len(labels)
+    rec["nlone"] = int(np.count_nonzero(nsite[labels] == 0)) if kind == L.SITEBOND else 0
+    rec["nspan"] = len(span)
+    if len(span):
+        first = span[np.argmin(minsite[span])]
+        rec["span_root"] = minsite[first]
+        rec["span_size"] = size[first]
+    rec["maxcs"] = s.max() if len(s) else 0
+    rec["s1"], rec["s2"] = s.sum(), (s * s).sum()
+    rec["span_s1"], rec["span_s2"] = size[span].sum(), (size[span] ** 2).sum()
+    hist = np.zeros(nexact + 32, dtype=np.int32)
+    if len(s):
+        np.add.at(hist, s[s <= nexact] - 1, 1)
+        np.add.at(hist, nexact + np.frexp(s)[1].astype(np.int64) - 1, 1)  # floor(log2 s), exactly
+    return rec, hist
+
+
 def _device_shuffle_ok(ctx, kind):
     """every list `kind` reads on ctx's lattice fits the shuffle kernel"""
     return ((kind == L.BOND or shuffle_device_supported(ctx.t))
@@ -589,6 +670,58 @@ class Context:
         L.check(getattr(L.lib(), name)(self.h, int(kind), int(scan), ntrials, L.ptr(so), L.ptr(bo),
                                        L.ptr(fx), C.cast(out, C.c_void_p)), name)
         return [{k: getattr(out[i], k) for k, _ in L.ScanItem._fields_} for i in range(ntrials)]
+
+    def batch_clusters(self, kind, item_trial, site_orders=None, bond_orders=None, item_nsites=None,
+                       item_nbonds=None, nexact=0, site_seeds=None, bond_seeds=None, hist=True):
+        """perc_batch_clusters: the cluster table's statistics of many small
+        (trial, nsites, nbonds) items in one launch, one workgroup each -- the
+        items, orders and counts of batch_cond.  Returns (records, hist): a
+        structured array (CLUSTER_DTYPE: nclusters, nlone, nspan, span_root,
+        span_size, maxcs, s1, s2, span_s1, span_s2) and the (nitems, nexact +
+        32) int32 histogram rows -- hist[i, s - 1] clusters of size s <= nexact,
+        hist[i, nexact + floor(log2 s)] every cluster (hist=False: no rows
+        are formed, None).  site_seeds / bond_seeds (one seed per trial) in
+        place of the order lists: perc_batch_clusters_seeded, the orders
+        shuffled on the device -- the same records."""
+        kind, nexact = int(kind), int(nexact)
+        it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
+        so = bo = ns = nbc = None
+        ntrials = None
+        seeded = site_seeds is not None or bond_seeds is not None
+        if seeded:
+            if site_orders is not None or bond_orders is not None:
+                raise ValueError("orders or seeds, not both")
+            if site_seeds is not None:
+                so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
+                ntrials = len(so)
+            if bond_seeds is not None:
+                bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
+                if ntrials is not None and len(bo) != ntrials:
+                    raise ValueError("site_seeds and bond_seeds differ in trials")
+                ntrials = len(bo)
+        if site_orders is not None:
+            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
+            ntrials = so.shape[0]
+        if bond_orders is not None:
+            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
+            if ntrials is not None and bo.shape[0] != ntrials:
+                raise ValueError("site_orders and bond_orders differ in trials")
+            ntrials = bo.shape[0]
+        if ntrials is None:
+            ntrials = int(it.max()) + 1 if len(it) else 0  # (no list at all: libperc reports it)
+        if item_nsites is not None:
+            ns = np.ascontiguousarray(item_nsites, dtype=np.int32).reshape(-1)
+        if item_nbonds is not None:
+            nbc = np.ascontiguousarray(item_nbonds, dtype=np.int32).reshape(-1)
+        for c in (ns, nbc):
+            if c is not None and c.shape != it.shape:
+                raise ValueError("item_trial and the count lists differ in length")
+        out = np.zeros(max(len(it), 1), dtype=L.CLUSTER_DTYPE)
+        hrows = np.zeros((max(len(it), 1), max(nexact, 0) + 32), dtype=np.int32) if hist else None
+        name = "perc_batch_clusters_seeded" if seeded else "perc_batch_clusters"
+        L.check(getattr(L.lib(), name)(self.h, kind, ntrials, L.ptr(so), L.ptr(bo), len(it), L.ptr(it),
+                                       L.ptr(ns), L.ptr(nbc), nexact, L.ptr(out), L.ptr(hrows)), name)
+        return out[:len(it)], (hrows[:len(it)] if hist else None)
 
     def bondc_realisation(self, order, tbonds, Va=1.0, g0=1.0, tol=1e-8, itmax=2500,
                           device_ptr=None):
@@ -1125,6 +1258,106 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
             ctx.close()
         elif large:
             ctx.set_batch_large(was_large)
+
+
+def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5, 0.6, 0.7), master=58302,
+                  numtrials=1, batch=256, nexact=64, device_shuffle=False, ctx=None, device=0):
+    """Cluster statistics as a function of p over trials: the cluster-size
+    distribution n_s(p), the moments behind the mean cluster size S(p), the
+    spanning clusters' share P_inf(p) and the clusters per site, for bond
+    (grid a list of pb), site (a list of ps) or mixed percolation (a list of
+    (ps, pb)).  Seeds and orders are cond_curve's: trial ii draws
+    shuffled_ids(nb, tseed(ii)) (BOND) or shuffled_ids(t, tseed(ii)) (SITE)
+    with trial_seeds(master), both lists with paired_seeds(master) for
+    SITEBOND; a grid point occupies the first int(ps * t) sites / int(pb * nb)
+    bonds.  batch > 0 on a lattice batch_clusters_supported accepts: about
+    `batch` (trial, point) items at a time (whole trials) through
+    Context.batch_clusters, with device_shuffle=True the orders shuffled on
+    the device from the seeds; batch=0, or another lattice: each item through
+    cluster_stats_host, no device at all (ctx is not used).  The same numbers
+    either way.  Returns (trials, stats, hist): per trial dict(ii, seed |
+    sseed, bseed, rows) with one row per grid point (p, counts and the record's
+    fields); stats (npts, 8) int64 {count, sum nclusters, count spanning, sum
+    span_size, sum s1, sum s2, sum span_s1, sum span_s2}; hist (npts, nexact +
+    32) int64, the items' histogram rows summed over the trials."""
+    if kind not in (L.BOND, L.SITE, L.SITEBOND):
+        raise ValueError("cluster_curve: kind BOND, SITE or SITEBOND")
+    if numtrials < 0:
+        raise ValueError("numtrials < 0")
+    if ctx is not None:
+        lattice, m, n, pbc = ctx.lattice, ctx.m, ctx.n, ctx.pbc
+    mixed = kind == L.SITEBOND
+    need_s, need_b = kind != L.BOND, kind != L.SITE
+    t, nb = m * n, nbonds(lattice, m, n, pbc)
+    pts = [(float(p[0]), float(p[1])) if mixed else ((float(p), None) if need_s else (None, float(p)))
+           for p in grid]
+    npts = len(pts)
+    cnt_s = np.array([int(ps * t) for ps, _ in pts], np.int32) if need_s else None
+    cnt_b = np.array([int(pb * nb) for _, pb in pts], np.int32) if need_b else None
+    if mixed:
+        ss, bs = paired_seeds(master, max(numtrials, 1))
+    elif need_s:
+        ss, bs = trial_seeds(master, max(numtrials, 1)), None
+    else:
+        ss, bs = None, trial_seeds(master, max(numtrials, 1))
+    batched = batch > 0 and npts > 0 and numtrials > 0 and batch_clusters_supported(lattice, m, n, pbc, nexact)
+    own = batched and ctx is None
+    if own:
+        ctx = Context(lattice, m, n, pbc, device)
+    try:
+        group = max(1, batch // max(npts, 1)) if batched else 1
+        seeded = batched and device_shuffle and _device_shuffle_ok(ctx, kind)
+        stats = np.zeros((npts, 8), dtype=np.int64)
+        hist = np.zeros((npts, nexact + 32), dtype=np.int64)
+        out = []
+        for i0 in range(0, numtrials, group):
+            tr = range(i0, min(i0 + group, numtrials))
+            so = bo = None
+            if not seeded:
+                so = np.stack([shuffled_ids(t, int(ss[ii])) for ii in tr]) if need_s else None
+                bo = np.stack([shuffled_ids(nb, int(bs[ii])) for ii in tr]) if need_b else None
+            if batched:
+                if seeded:
+                    src = dict(site_seeds=ss[tr.start:tr.stop] if need_s else None,
+                               bond_seeds=bs[tr.start:tr.stop] if need_b else None)
+                else:
+                    src = dict(site_orders=so, bond_orders=bo)
+                recs, rows = ctx.batch_clusters(kind, np.repeat(np.arange(len(tr), dtype=np.int32), npts), **src,
+                                                item_nsites=np.tile(cnt_s, len(tr)) if need_s else None,
+                                                item_nbonds=np.tile(cnt_b, len(tr)) if need_b else None,
+                                                nexact=nexact)
+            else:
+                recs = np.zeros(len(tr) * npts, dtype=L.CLUSTER_DTYPE)
+                rows = np.zeros((len(tr) * npts, nexact + 32), dtype=np.int32)
+                for k in range(len(tr)):
+                    for j in range(npts):
+                        recs[k * npts + j], rows[k * npts + j] = cluster_stats_host(
+                            lattice, m, n, pbc, kind, so[k] if need_s else None, int(cnt_s[j]) if need_s else 0,
+                            bo[k] if need_b else None, int(cnt_b[j]) if need_b else 0, nexact)
+            for k, ii in enumerate(tr):
+                trows = []
+                for j, (ps, pb) in enumerate(pts):
+                    r = recs[k * npts + j]
+                    row = {}
+                    if need_s:
+                        row.update(ps=ps, nsites=int(cnt_s[j]))
+                    if need_b:
+                        row.update(pb=pb, nbonds=int(cnt_b[j]))
+                    row.update({f: int(r[f]) for f in L.CLUSTER_DTYPE.names})
+                    trows.append(row)
+                    stats[j] += (1, r["nclusters"], int(r["nspan"] > 0), r["span_size"], r["s1"], r["s2"],
+                                 r["span_s1"], r["span_s2"])
+                    hist[j] += rows[k * npts + j]
+                trial = dict(ii=ii + 1, rows=trows)
+                if mixed:
+                    trial.update(sseed=int(ss[ii]), bseed=int(bs[ii]))
+                else:
+                    trial.update(seed=int((ss if need_s else bs)[ii]))
+                out.append(trial)
+        return out, stats, hist
+    finally:
+        if own:
+            ctx.close()
 
 
 # ---------------------------------------------------------------- file output

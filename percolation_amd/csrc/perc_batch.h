@@ -4,8 +4,9 @@
 // dev_batch_run and k_batch_cond; perc_batch_large.hip and
 // perc_batch_weighted.hip their kernel and its launch; perc_batch_item.h the
 // device code the three kernels share (the item's front end, the workgroup
-// sums, the electrode rows' currents); perc_batch_host.cpp the C-ABI, the LDS
-// plans and the ensemble's batched trial loop.
+// sums, the electrode rows' currents); perc_batch_scan.hip, perc_batch_clusters.hip
+// and perc_batch_shuffle.hip their kernels and buffers; perc_batch_host.cpp the
+// C-ABI, the LDS plans and the ensemble's batched trial loop.
 #pragma once
 #include <type_traits>
 
@@ -256,6 +257,38 @@ void dev_scan_free(perc_ctx* h);
 const int* dev_batch_ranks(perc_ctx* h, int* ntrials);
 // the same for the site ranks dev_batch_upload_sites left
 const int* dev_batch_site_ranks(perc_ctx* h, int* ntrials);
+// ---- cluster statistics (perc_batch_clusters.hip: k_batch_clusters) -----
+// the exact part of an item's histogram row: sizes 1..nexact, nexact at most
+constexpr int kClusterExactMax = 1024;
+// Byte offsets of k_batch_clusters' LDS arena (every offset a multiple of
+// 16): the scan's arena (scan_lds: parent, the per-root sizes, the link
+// bytes, the spanning flags, 16 ints), then the histogram row (nexact + 32
+// ints) and the waves' partial sums (16 waves x 9 words of 8 bytes).
+struct ClusterLds {
+  int oSize, oLink, oFlag, oInt, oHist, oRed, total;
+};
+ClusterLds cluster_lds(const Geom& g, int nexact);
+constexpr int kClusterLdsStatic = 256;  // the compiler's own static LDS of k_batch_clusters (resource usage)
+// host-only check of perc_batch_clusters_supported: the scan's lattices, and
+// 0 <= nexact <= kClusterExactMax
+bool clusters_supported(const Geom& g, int nexact);
+// device side.  nitems items over rank arrays in device memory (d_rank_b:
+// ntrials x nb, d_rank_s: ntrials x t; either may be NULL where the kind does
+// not read it; every item_trial lies inside them: the caller's check); the
+// item lists, out (nitems) and hist (nitems x (nexact + 32), or NULL) on the
+// host.  Threads per workgroup: scan_threads(t).
+hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank_s, const int* d_rank_b,
+                            const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                            int nexact, perc_cluster_item* out, int* hist);
+// pinned host arrays of ns / nbk ints (either may be 0: NULL) for the call to
+// form a launch's rank arrays in; they live with the kernel's buffers
+hipError_t dev_clusters_stage(perc_ctx* h, size_t ns, size_t nbk, int** rank_s, int** rank_b);
+// rank arrays of the call's own orders (host, ntrials x t / ntrials x nb,
+// either NULL) uploaded into the kernel's buffers, then dev_clusters_run
+hipError_t dev_clusters_upload_run(perc_ctx* h, int kind, int ntrials, const int* rank_s, const int* rank_b,
+                                   int nitems, const int* item_trial, const int* item_nsites,
+                                   const int* item_nbonds, int nexact, perc_cluster_item* out, int* hist);
+void dev_clusters_free(perc_ctx* h);
 // ---- device shuffle (perc_batch_shuffle.hip: k_shuffle_ranks) -----------
 // Byte offsets of k_shuffle_ranks' LDS arena (every offset a multiple of 16):
 // the order (16-bit ids, N + 1) at 0, the swap targets of 64 steps (int).

@@ -4,7 +4,8 @@
 // perc_scan_supported, perc_batch_scan and the seeded forms
 // perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded, and the
 // weighted perc_batch_weighted_supported, perc_batch_cond_weighted,
-// perc_batch_twister):
+// perc_batch_twister, and the cluster tables' perc_batch_clusters_supported,
+// perc_batch_clusters, perc_batch_clusters_seeded):
 // argument checks, the orders' inverse permutations, the
 // launch geometry and LDS layouts, the fold of the terminal currents and the
 // single-path replay of the items several clusters span.
@@ -181,6 +182,21 @@ int scan_threads(int t) { return t <= 256 * kScanSPT ? 256 : (t <= 512 * kScanSP
 bool scan_supported(const Geom& g) {
   if (g.n < 3 || g.m < 3 || (long long)g.m * g.n > kScanSites) return false;
   return scan_lds(g).total + kScanLdsStatic <= kBatchLdsMax;
+}
+
+ClusterLds cluster_lds(const Geom& g, int nexact) {
+  const ScanLds S = scan_lds(g);
+  ClusterLds L{};
+  L.oSize = S.oSize, L.oLink = S.oLink, L.oFlag = S.oFlag, L.oInt = S.oInt;
+  L.oHist = S.total;
+  L.oRed = L.oHist + up16(4 * ((long long)nexact + 32));
+  L.total = L.oRed + 16 * 9 * 8;
+  return L;
+}
+
+bool clusters_supported(const Geom& g, int nexact) {
+  if (nexact < 0 || nexact > kClusterExactMax || !scan_supported(g)) return false;
+  return cluster_lds(g, nexact).total + kClusterLdsStatic <= kBatchLdsMax;
 }
 
 ShuffleLds shuffle_lds(int N) {
@@ -703,6 +719,119 @@ int perc_batch_scan_seeded(perc_ctx* h, int kind, int scan, int ntrials, const i
                            const int* bond_seeds, const int* fixed, perc_scan_item* out) {
   return batch_scan_impl("perc_batch_scan_seeded", true, h, kind, scan, ntrials, site_seeds, bond_seeds,
                          fixed, out);
+}
+
+int perc_batch_clusters_supported(int lattice, int m, int n, int pbc, int nexact) {
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n > kScanSites) return 0;
+  return clusters_supported(make_geom(lattice, m, n, pbc), nexact) ? 1 : 0;
+}
+
+// perc_batch_clusters (seeded = false: site_src / bond_src are order lists)
+// and perc_batch_clusters_seeded (true: seed lists, the orders shuffled on the
+// device).  A launch takes a run of items and the trials they name, numbered
+// afresh in order of first use: a run of k items names at most k trials, so
+// the bound on the run bounds the launch's rank arrays too.
+static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int kind, int ntrials,
+                               const int* site_src, const int* bond_src, int nitems, const int* item_trial,
+                               const int* item_nsites, const int* item_nbonds, int nexact,
+                               perc_cluster_item* out, int* hist) {
+  if (!h) return PERC_EINVAL;
+  auto bad = [who](const char* text) {
+    set_error(std::string(who) + ": " + text);
+    return PERC_EINVAL;
+  };
+  if (kind != PERC_BOND && kind != PERC_SITE && kind != PERC_SITEBOND)
+    return bad("kind PERC_BOND, PERC_SITE or PERC_SITEBOND only");
+  if (ntrials < 0 || nitems < 0) return bad("ntrials or nitems < 0");
+  if (nexact < 0 || nexact > kClusterExactMax) return bad("nexact outside 0..1024");
+  if (!clusters_supported(h->g, nexact))
+    return bad("lattice not supported by the cluster kernel (perc_batch_clusters_supported)");
+  const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
+  if (ntrials && ((need_s && !site_src) || (need_b && !bond_src)))
+    return bad(seeded ? "a seed list the kind reads is missing" : "an order list the kind reads is missing");
+  if (nitems && (!item_trial || !out || (need_s && !item_nsites) || (need_b && !item_nbonds)))
+    return bad("item_trial, out or a count list the kind reads is missing");
+  const int t = h->g.t, nb = (int)h->nb;
+  for (int i = 0; i < nitems; ++i) {
+    if (item_trial[i] < 0 || item_trial[i] >= ntrials) return bad("item_trial outside 0..ntrials-1");
+    if (need_s && (item_nsites[i] < 0 || item_nsites[i] > t + 1)) return bad("item_nsites outside 0..t+1");
+    if (need_b && (item_nbonds[i] < 0 || item_nbonds[i] > nb + 1)) return bad("item_nbonds outside 0..nb+1");
+  }
+  if (seeded && ((need_s && !shuffle_supported(t)) || (need_b && !shuffle_supported(nb))))
+    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (nitems == 0) return PERC_OK;
+  hipSetDevice(h->device);
+  // launches whose rank arrays and histogram rows each stay under 64 MB
+  const long long per = 4LL * ((need_s ? t : 0) + (need_b ? nb : 0));
+  const long long nh = (long long)nexact + 32;
+  const int chunk = (int)std::max(1LL, std::min({(long long)nitems, (64LL << 20) / per, (64LL << 20) / (4 * nh)}));
+  std::vector<int> local((size_t)ntrials, -1), used, ltrial((size_t)chunk), seeds_s, seeds_b;
+  for (int i0 = 0; i0 < nitems; i0 += chunk) {
+    const int n = std::min(chunk, nitems - i0);
+    for (int tr : used) local[tr] = -1;
+    used.clear();
+    for (int i = 0; i < n; ++i) {
+      const int tr = item_trial[i0 + i];
+      if (local[tr] < 0) {
+        local[tr] = (int)used.size();
+        used.push_back(tr);
+      }
+      ltrial[i] = local[tr];
+    }
+    const int k = (int)used.size();
+    const int* ns = need_s ? item_nsites + i0 : nullptr;
+    const int* nbc = need_b ? item_nbonds + i0 : nullptr;
+    int* hrow = hist ? hist + (size_t)i0 * nh : nullptr;
+    hipError_t e = hipSuccess;
+    if (seeded) {
+      // the run's trials shuffled straight into the batch path's rank buffers
+      if (need_s) {
+        seeds_s.resize(k);
+        for (int j = 0; j < k; ++j) seeds_s[j] = site_src[used[j]];
+        e = dev_shuffle_run(h, PERC_SITE, k, seeds_s.data(), nullptr, nullptr);
+      }
+      if (e == hipSuccess && need_b) {
+        seeds_b.resize(k);
+        for (int j = 0; j < k; ++j) seeds_b[j] = bond_src[used[j]];
+        e = dev_shuffle_run(h, PERC_BOND, k, seeds_b.data(), nullptr, nullptr);
+      }
+      int have_s = 0, have_b = 0;
+      const int* d_s = need_s ? dev_batch_site_ranks(h, &have_s) : nullptr;
+      const int* d_b = need_b ? dev_batch_ranks(h, &have_b) : nullptr;
+      if (e == hipSuccess)
+        e = dev_clusters_run(h, kind, n, d_s, d_b, ltrial.data(), ns, nbc, nexact, out + i0, hrow);
+    } else {
+      int *rank_s = nullptr, *rank_b = nullptr;
+      e = dev_clusters_stage(h, need_s ? (size_t)k * t : 0, need_b ? (size_t)k * nb : 0, &rank_s, &rank_b);
+      if (e != hipSuccess) return hip_status(e, who);
+      if (need_s)
+        for (int j = 0; j < k; ++j)
+          order_ranks(1, t, site_src + (size_t)used[j] * (t + 1), rank_s + (size_t)j * t);
+      if (need_b)
+        for (int j = 0; j < k; ++j)
+          order_ranks(1, nb, bond_src + (size_t)used[j] * (nb + 1), rank_b + (size_t)j * nb);
+      e = dev_clusters_upload_run(h, kind, k, need_s ? rank_s : nullptr, need_b ? rank_b : nullptr, n,
+                                  ltrial.data(), ns, nbc, nexact, out + i0, hrow);
+    }
+    if (e != hipSuccess) return hip_status(e, who);
+  }
+  return PERC_OK;
+}
+
+int perc_batch_clusters(perc_ctx* h, int kind, int ntrials, const int* site_orders, const int* bond_orders,
+                        int nitems, const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                        int nexact, perc_cluster_item* out, int* hist) {
+  return batch_clusters_impl("perc_batch_clusters", false, h, kind, ntrials, site_orders, bond_orders, nitems,
+                             item_trial, item_nsites, item_nbonds, nexact, out, hist);
+}
+
+int perc_batch_clusters_seeded(perc_ctx* h, int kind, int ntrials, const int* site_seeds,
+                               const int* bond_seeds, int nitems, const int* item_trial,
+                               const int* item_nsites, const int* item_nbonds, int nexact,
+                               perc_cluster_item* out, int* hist) {
+  return batch_clusters_impl("perc_batch_clusters_seeded", true, h, kind, ntrials, site_seeds, bond_seeds,
+                             nitems, item_trial, item_nsites, item_nbonds, nexact, out, hist);
 }
 
 }  // extern "C"

@@ -49,43 +49,12 @@ __global__ __launch_bounds__(NT) void k_batch_scan(ScanArgs a) {
   int npass = 0, nlabel = 0;  // (probe builds report them)
   // ---- one labeling at scanned count c (uniform): an element is occupied
   // iff its position in the order < its list's count.  The ranks are read
-  // once, into one link byte per site (bit k: the forward bond to nearestn
-  // slot k connects; bit 7: member site); the hook passes read LDS only.
+  // once, into one link byte per site (lds_links); the hook passes read LDS
+  // only.
   auto label = [&](int c) {
     const int cs = scan_sites ? c : fx;  // (site kinds)
     const int cb = scan_sites ? fx : c;  // (bond and mixed kinds)
-    for (int s = t; s <= T; s += NT) parent[s] = s;
-    if constexpr (KIND != PERC_BOND) {
-      // the site occupancy, for the neighbours' threads (size is free until
-      // the sizes are formed)
-      for (int s = t + 1; s <= T; s += NT) size[s] = rs[s - 1] < cs ? 1 : 0;
-      __syncthreads();
-    }
-    for (int s = t + 1; s <= T; s += NT) {
-      const int sr = div_m(g, s - 1);
-      int nn[6];
-      nearestn_rc(g, s, sr, s - 1 - sr * m, nn);
-      unsigned lk = 0;
-      bool on = true;
-      if constexpr (KIND != PERC_BOND) {
-        on = size[s] != 0;
-        lk = on ? 0x80u : 0u;
-      }
-      if (on) {
-        int id = a.bond_first[s];
-        for (int k = 0; k < g.scn; ++k) {
-          const int q = nn[k];
-          if (q <= s) continue;
-          bool con = true;
-          if constexpr (KIND != PERC_BOND) con = size[q] != 0;
-          if constexpr (KIND != PERC_SITE) con = con && rb[id] < cb;
-          lk |= (con ? 1u : 0u) << k;
-          ++id;
-        }
-      }
-      link[s] = (uint8_t)lk;
-    }
-    __syncthreads();
+    lds_links<NT, KIND>(g, a.bond_first, rs, rb, cs, cb, parent, size, link);
     npass += lds_label<NT>(g, a.bond_first, parent,
                            [&](int, int s, int k, int, int) { return (link[s] >> k & 1) != 0; });
     ++nlabel;
@@ -122,13 +91,8 @@ __global__ __launch_bounds__(NT) void k_batch_scan(ScanArgs a) {
     const int r = parent[T - m + 1 + c];
     if (r <= m) flag[r] = 1;
   }
-  if constexpr (KIND != PERC_SITEBOND) {
-    for (int s = t + 1; s <= T; s += NT) {
-      const unsigned lk = link[s];
-      const int c = KIND == PERC_BOND ? __popc(lk & 0x3fu) : (int)(lk >> 7);
-      if (c) atomicAdd(&size[parent[s]], c);
-    }
-  }
+  if constexpr (KIND != PERC_SITEBOND)
+    (void)lds_root_sizes<NT, KIND>(g, a.bond_first, rb, 0, parent, link, size);
   __syncthreads();
   {
     int nsp = 0, mn = INT_MAX, mx = 0;

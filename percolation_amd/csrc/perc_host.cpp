@@ -277,6 +277,7 @@ int perc_ctx_destroy(perc_ctx* h) {
   dev_batch_free(h);
   dev_scan_free(h);
   dev_shuffle_free(h);
+  dev_clusters_free(h);
   free_buffers(h);
   for (int i = 0; i < 8; ++i)
     if (h->ev[i]) hipEventDestroy(h->ev[i]);

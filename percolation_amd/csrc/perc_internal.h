@@ -269,6 +269,7 @@ struct perc_ctx {
   int w_lds[3][2][3] = {};   // ... of k_batch_cond_w (perc_batch_weighted.hip)
   void* scan = nullptr;    // perc_batch_scan's device buffers (perc_batch_scan.hip), made on first use
   void* shuffle = nullptr; // perc_batch_shuffle's device buffers (perc_batch_shuffle.hip), made on first use
+  void* clusters = nullptr; // perc_batch_clusters' device buffers (perc_batch_clusters.hip), made on first use
 };
 
 namespace perc {

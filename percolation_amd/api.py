@@ -898,14 +898,20 @@ def pb_grid(lattice, nb):
     return (pbarr * nb).astype(np.int64).astype(np.int32)  # truncation (H3 repeats kept)
 
 
-def first_spanning(ctx, order, kind=L.BOND, n=None):
+def first_spanning(ctx, order, kind=L.BOND, n=None, on_device=False):
     """Smallest count c such that occupying order[:c] spans (the pc step of
     bond_cond.f:381; bond_perc.f / site_perc.f), 0 if none: perc_first_spanning,
-    a bisection with the GPU labeling.  The context is left occupied at c."""
+    a bisection with the GPU labeling.  The context is left occupied at c.
+    on_device: `order` is the int address of a device int32 array on the
+    context's device (kept alive by the caller while the context uses it)."""
     n = (ctx.nb if kind == L.BOND else ctx.t) if n is None else n
-    o = np.ascontiguousarray(order[:n], dtype=np.int32)
     first = C.c_int()
-    L.check(L.lib().perc_first_spanning(ctx.h, kind, L.ptr(o), n, 0, C.byref(first)),
+    if on_device:
+        src = C.c_void_p(order) if order else None
+    else:
+        o = np.ascontiguousarray(order[:n], dtype=np.int32)
+        src = L.ptr(o)
+    L.check(L.lib().perc_first_spanning(ctx.h, kind, src, n, 1 if on_device else 0, C.byref(first)),
             "perc_first_spanning")
     return first.value
 
@@ -965,14 +971,22 @@ def threshold_scan(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, master=58302, numt
             ctx.close()
 
 
-def first_spanning_mixed(ctx, scan, site_order, nsites, bond_order, nbonds):
+def first_spanning_mixed(ctx, scan, site_order, nsites, bond_order, nbonds, on_device=False):
     """perc_first_spanning_mixed: sites fixed and bonds scanned (scan=BOND,
-    sb_perc) or bonds fixed and sites scanned (scan=SITE, bs_perc)."""
-    so = np.ascontiguousarray(site_order[:max(nsites, 1)], dtype=np.int32)
-    bo = np.ascontiguousarray(bond_order[:max(nbonds, 1)], dtype=np.int32)
+    sb_perc) or bonds fixed and sites scanned (scan=SITE, bs_perc).
+    on_device: site_order and bond_order are the int addresses of device
+    int32 arrays on the context's device."""
     first = C.c_int()
-    L.check(L.lib().perc_first_spanning_mixed(ctx.h, scan, L.ptr(so), nsites, L.ptr(bo), nbonds,
-                                              0, C.byref(first)), "perc_first_spanning_mixed")
+    if on_device:
+        sp = C.c_void_p(site_order) if site_order else None
+        bp = C.c_void_p(bond_order) if bond_order else None
+    else:
+        so = np.ascontiguousarray(site_order[:max(nsites, 1)], dtype=np.int32)
+        bo = np.ascontiguousarray(bond_order[:max(nbonds, 1)], dtype=np.int32)
+        sp, bp = L.ptr(so), L.ptr(bo)
+    L.check(L.lib().perc_first_spanning_mixed(ctx.h, scan, sp, nsites, bp, nbonds,
+                                              1 if on_device else 0, C.byref(first)),
+            "perc_first_spanning_mixed")
     return first.value
 
 

@@ -937,6 +937,79 @@ int perc_batch_clusters_seeded(perc_ctx *h, int kind, int ntrials,
                                const int *item_nbonds, int nexact, perc_cluster_item *out,
                                int *hist);
 
+/* ---- batch current distributions (one workgroup per item) ------------- *
+ * perc_batch_cond returns Gtop and Gbot and drops the voltages between them.
+ * perc_batch_cond_currents is perc_batch_cond (it always solves) that also
+ * says where the current flows: per item one perc_batch_currents record and,
+ * where vint_out is given, the interior voltages -- what a user of the
+ * reference's ConductCalc otherwise forms with a loop of their own over the
+ * bond list, one realisation at a time.
+ * Definition.  V: 0 on the bottom row, Va on the top row, the interior
+ * solution x elsewhere (row i of the system is site i + m + 1).  A bond is
+ * conducting when the kind's rule gives it g0 (occupied as the kind asks, and
+ * in the chosen spanning cluster).  Counted, each once: the conducting bonds
+ * with at least one interior end site (a bond inside an electrode row has
+ * zero drop by construction).  Per bond i_b = g0 * (V[b2] - V[b1]), one
+ * subtraction and one multiplication; only |i_b| is used.
+ * nbonds, nabove, imax and hist are exact functions of the voltages' bits.
+ * The four sums have no literal reference order: on the device each thread
+ * sums its rows in row order with slots ascending and the workgroup's fixed
+ * tree combines them -- deterministic and independent of the item's place in
+ * the launch under both dot orders; perc_current_stats_host sums in bond-id
+ * order.  The two agree to rounding ((nbonds + 8) ulp relative), not bitwise.
+ * cut: the backbone at cut is the bonds with |i| >= cut * imax.  A dangling
+ * end of the spanning cluster carries no current, but the solve leaves it the
+ * residual's noise: about 1e-9 of imax at tol = 1e-8, about 1e-12 at a tight
+ * tol.  cut must sit above that noise -- the caller's choice of tol decides
+ * how small a cut still separates the backbone.
+ * The default kernel only (k_batch_cond, at most 8192 interior rows): the
+ * large kernel keeps x on 2m rows and the weighted one has other bond values,
+ * so neither has this form, and the calls do not read the
+ * perc_set_batch_large flag.  out is filled exactly as perc_batch_cond fills
+ * it.  An item no cluster spans has an all-zero record and zero voltages.  An
+ * item several clusters span (fallback = 1) runs through perc_occupy /
+ * perc_label / perc_conductance on the context and perc_current_stats_host,
+ * and leaves the context as perc_batch_cond does.  The call chunks itself as
+ * perc_batch_cond, with 8 N more bytes per item against the 64 MB bound when
+ * vint_out is given.  PERC_EINVAL (text in perc_last_error), before any
+ * device call: perc_batch_cond's cases, cur == NULL, cut outside [0, 1] or
+ * NaN, a lattice perc_batch_currents_supported refuses for the kind. */
+typedef struct {
+  int nbonds;              /* conducting bonds counted                       */
+  int nabove;              /* of them, |i| >= cut * imax  (the backbone at cut) */
+  double imax;             /* max |i|                                        */
+  double s1, s2, s4, s6;   /* sum |i|, i^2, i^4, i^6  (i2 = i*i, i4 = i2*i2, i6 = i4*i2) */
+  int hist[64];            /* octaves: bin = clamp(ilogb(g0*Va) - ilogb(|i|), 0, 63); |i| == 0 -> 63 */
+} perc_batch_currents;
+/* host-only: exactly perc_batch_cond_supported */
+int perc_batch_currents_supported(int kind, int lattice, int m, int n, int pbc);
+int perc_batch_cond_currents(perc_ctx *h, int kind, int rule, int cur_rule, int ntrials,
+                             const int *site_orders /* ntrials x (t+1), NULL for PERC_BOND */,
+                             const int *bond_orders /* ntrials x (nb+1), NULL for PERC_SITE */,
+                             int nitems, const int *item_trial,
+                             const int *item_nsites /* NULL for PERC_BOND */,
+                             const int *item_nbonds /* NULL for PERC_SITE */,
+                             double Va, double g0, double leak, int itol, double tol, int itmax,
+                             perc_batch_item *out, double cut, perc_batch_currents *cur /* nitems */,
+                             double *vint_out /* nitems x N, or NULL */);
+/* the same with seed lists (one seed per trial), the orders shuffled on the
+   device: the same records item for item */
+int perc_batch_cond_currents_seeded(perc_ctx *h, int kind, int rule, int cur_rule, int ntrials,
+                                    const int *site_seeds /* ntrials, NULL for PERC_BOND */,
+                                    const int *bond_seeds /* ntrials, NULL for PERC_SITE */,
+                                    int nitems, const int *item_trial, const int *item_nsites,
+                                    const int *item_nbonds, double Va, double g0, double leak,
+                                    int itol, double tol, int itmax, perc_batch_item *out,
+                                    double cut, perc_batch_currents *cur, double *vint_out);
+/* The record of one realisation on the host (no device): the bond list in id
+   order, conducting[id - 1] != 0 the conducting bonds, vint the t - 2m
+   interior voltages, the sums in bond-id order.  PERC_EINVAL: a bad lattice,
+   m or n < 1, a NULL array, cut outside [0, 1] or NaN. */
+int perc_current_stats_host(int lattice, int m, int n, int pbc,
+                            const unsigned char *conducting /* nb, by bond id */,
+                            const double *vint, double Va, double g0, double cut,
+                            perc_batch_currents *out);
+
 /* ---- ensemble statistics (bond_cond, config 4) ----------------------- */
 /* Accumulate stats for one pb point: {count, sum G, sum G^2, count spanning,
    sum iter} into acc[5*point..]. */

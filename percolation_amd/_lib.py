@@ -73,6 +73,14 @@ CLUSTER_DTYPE = np.dtype([("nclusters", np.int32), ("nlone", np.int32), ("nspan"
 assert CLUSTER_DTYPE.itemsize == C.sizeof(ClusterItem) == 56
 
 
+# perc_batch_currents as a numpy record (Context.batch_cond(currents=True), api.current_stats_host)
+CURRENTS_DTYPE = np.dtype([("nbonds", np.int32), ("nabove", np.int32), ("imax", np.float64),
+                           ("s1", np.float64), ("s2", np.float64), ("s4", np.float64), ("s6", np.float64),
+                           ("hist", np.int32, (64,))])
+assert CURRENTS_DTYPE.itemsize == 304
+CURRENTS_KEYS = ("nbonds", "nabove", "imax", "s1", "s2", "s4", "s6", "hist")
+
+
 class DslabBufs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("part_out", "part_all", "edge_lo", "edge_hi",
                                           "ghost_lo", "ghost_hi")]
@@ -225,6 +233,14 @@ SIGNATURES = {
                                       _VP]),
     "perc_batch_clusters_seeded": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int,
                                              _VP, _VP]),
+    "perc_batch_currents_supported": (C.c_int, [C.c_int] * 5),
+    "perc_batch_cond_currents": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP,
+                                           _VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int,
+                                           C.c_double, C.c_int, _VP, C.c_double, _VP, _VP]),
+    "perc_batch_cond_currents_seeded": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int,
+                                                  _VP, _VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                  C.c_double, C.c_int, _VP, C.c_double, _VP, _VP]),
+    "perc_current_stats_host": (C.c_int, [C.c_int] * 4 + [_VP, _VP, C.c_double, C.c_double, C.c_double, _VP]),
     "perc_ensemble_ctx": (C.c_void_p, [_VP, C.c_int]),
     "perc_ensemble_trials": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP]),
     "perc_ensemble_allreduce": (C.c_int, [_VP, _D, C.c_int]),

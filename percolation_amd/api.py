@@ -11,6 +11,9 @@ parameter names and semantics:
   cond_curve site / sitebond realisations over trials and a grid of ps or
              (ps, pb): the mean ConductCalc.m conductance curve (no reference
              program; the batch kernel's ensemble, Context.batch_cond)
+  current_curve  the same trials' bond-current statistics over a grid of p:
+             backbone fraction, current moments, histogram
+             (Context.batch_cond(currents=True))
 
 Every compute step runs in libperc on the GPU; there is no fallback.
 """
@@ -152,6 +155,60 @@ def batch_clusters_supported(lattice, m, n, pbc=0, nexact=0):
     (Context.batch_clusters) can run this lattice with this exact range --
     what scan_supported accepts, and 0 <= nexact <= 1024."""
     return bool(L.lib().perc_batch_clusters_supported(lattice, m, n, pbc, int(nexact)))
+
+
+def batch_currents_supported(kind, lattice, m, n, pbc=0):
+    """perc_batch_currents_supported (host-only): True when
+    Context.batch_cond(currents=True) can run this kind on this lattice --
+    exactly batch_cond_supported (the default kernel only, at most 8192
+    interior rows; set_batch_large is not read)."""
+    return bool(L.lib().perc_batch_currents_supported(int(kind), lattice, m, n, pbc))
+
+
+def _currents_dict(rec):
+    """one CURRENTS_DTYPE record as the keys Context.batch_cond adds"""
+    d = {k: rec[k].item() for k in L.CURRENTS_KEYS[:-1]}
+    d["hist"] = np.array(rec["hist"], dtype=np.int32)
+    return d
+
+
+def current_stats_host(lattice, m, n, pbc, conducting, vint, Va=1.0, g0=1.0, cut=1e-6):
+    """perc_current_stats_host (host-only, no device): the bond-current record
+    of one realisation -- over the conducting bonds (conducting[id - 1] != 0,
+    nb entries by bond id) with an interior end site, |i| = |g0 (V[b2] -
+    V[b1])| with V = 0 on the bottom row, Va on the top row and vint (t - 2m)
+    between: dict(nbonds, nabove, imax, s1, s2, s4, s6, hist), the sums in
+    bond-id order, nabove the bonds with |i| >= cut * imax, hist[64] the
+    octaves below g0 Va."""
+    nb = nbonds(lattice, m, n, pbc) if m >= 1 and n >= 1 else 0
+    c = np.ascontiguousarray(conducting, dtype=np.uint8).reshape(-1)
+    v = np.ascontiguousarray(vint, dtype=np.float64).reshape(-1)
+    if len(c) != nb or len(v) != max(m * n - 2 * m, 0):
+        raise ValueError("current_stats_host: conducting has nb entries, vint t - 2m")
+    rec = np.zeros(1, dtype=L.CURRENTS_DTYPE)
+    L.check(L.lib().perc_current_stats_host(lattice, m, n, pbc, L.ptr(c), L.ptr(v), float(Va), float(g0),
+                                            float(cut), L.ptr(rec)), "perc_current_stats_host")
+    return _currents_dict(rec[0])
+
+
+def conducting_bonds(kind, b1, b2, site_occ, bond_occ, canon, root):
+    """The conducting bonds of a labeled realisation (uint8, nb entries by bond
+    id): the bonds the kind's rule gives g0 -- BOND: the bond is occupied;
+    SITE: both end sites are; SITEBOND: the bond and both end sites are -- and
+    whose end sites lie in the chosen spanning cluster (canon[s - 1] == root,
+    Context.label(canon=True); root 0: none).  b1, b2: bond_list; site_occ,
+    bond_occ: Context.occupancy()."""
+    kind = int(kind)
+    if kind not in (L.BOND, L.SITE, L.SITEBOND):
+        raise ValueError("conducting_bonds: kind BOND, SITE or SITEBOND")
+    b1, b2 = np.asarray(b1, dtype=np.int64) - 1, np.asarray(b2, dtype=np.int64) - 1
+    so, bo, canon = np.asarray(site_occ) != 0, np.asarray(bond_occ) != 0, np.asarray(canon)
+    occ = np.ones(len(b1), dtype=bool)
+    if kind != L.SITE:
+        occ &= bo
+    if kind != L.BOND:
+        occ &= so[b1] & so[b2]
+    return (occ & (int(root) > 0) & (canon[b1] == int(root))).astype(np.uint8)
 
 
 def _whole_prefix(order, count, N):
@@ -528,7 +585,7 @@ class Context:
     def batch_cond(self, kind, item_trial, site_orders=None, bond_orders=None, item_nsites=None,
                    item_nbonds=None, rule=None, cur_rule=None, solve=True, Va=1.0, g0=1.0, leak=LEAK,
                    itol=2, tol=1e-8, itmax=2500, site_seeds=None, bond_seeds=None, weights=None,
-                   item_wset=None, item_wseed=None):
+                   item_wset=None, item_wseed=None, currents=False, cut=1e-6, voltages=False):
         """perc_batch_cond: many small bond, site or mixed realisations in one
         launch, one workgroup each.  kind BOND: bond_orders (ntrials, nb + 1)
         and item_nbonds; SITE: site_orders (ntrials, t + 1) and item_nsites;
@@ -545,8 +602,22 @@ class Context:
         that keeps the rows' values -- weights (nwsets, nb) per-bond multipliers
         with item_wset[i] the row item i uses (set_bond_weights(row) per item),
         or item_wseed[i] the rand('twister') seed item i draws with
-        (set_conductcalc_weights(rule, seed) per item); order lists only."""
+        (set_conductcalc_weights(rule, seed) per item); order lists only.
+        currents=True: perc_batch_cond_currents (or its seeded form) -- every
+        item's dict gains the bond-current record of current_stats_host
+        (nbonds, nabove at `cut`, imax, s1, s2, s4, s6, hist as an int array;
+        all zero where nothing spans) and, with voltages=True, vint (N
+        doubles).  The default kernel only (batch_currents_supported); not
+        with weights, not with solve=False.  cut must sit above the solver's
+        noise on the dangling ends: about 1e-9 of imax at tol=1e-8."""
         kind = int(kind)
+        weighted = weights is not None or item_wset is not None or item_wseed is not None
+        if currents and weighted:
+            raise ValueError("currents=True does not go with weights / item_wset / item_wseed")
+        if currents and not solve:
+            raise ValueError("currents=True always solves (no solve=False)")
+        if voltages and not currents:
+            raise ValueError("voltages=True goes with currents=True")
         if rule is None:
             rule = KIND_RULE.get(kind, -1)  # (an unknown kind: libperc reports it)
         if cur_rule is None:
@@ -604,6 +675,26 @@ class Context:
                 1 if solve else 0, Va, g0, leak, itol, tol, itmax, C.cast(out, C.c_void_p)),
                 "perc_batch_cond_weighted")
             return [{k: getattr(out[i], k) for k, _ in L.BatchItem._fields_} for i in range(len(it))]
+        if currents:
+            name = "perc_batch_cond_currents_seeded" if seeded else "perc_batch_cond_currents"
+            cur = np.zeros(max(len(it), 1), dtype=L.CURRENTS_DTYPE)
+            vint = np.zeros((max(len(it), 1), self.N), dtype=np.float64) if voltages else None
+            L.check(getattr(L.lib(), name)(self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so),
+                                           L.ptr(bo), len(it), L.ptr(it), L.ptr(ns), L.ptr(nbc), Va, g0, leak,
+                                           itol, tol, itmax, C.cast(out, C.c_void_p), float(cut), L.ptr(cur),
+                                           L.ptr(vint)), name)
+            cols = [(k, cur[k].tolist()) for k in L.CURRENTS_KEYS[:-1]]  # (columns at once: no per-item numpy)
+            hist = cur["hist"].copy()
+            res = []
+            for i in range(len(it)):
+                d = {k: getattr(out[i], k) for k, _ in L.BatchItem._fields_}
+                for k, col in cols:
+                    d[k] = col[i]
+                d["hist"] = hist[i]
+                if voltages:
+                    d["vint"] = vint[i]
+                res.append(d)
+            return res
         name = "perc_batch_cond_seeded" if seeded else "perc_batch_cond"
         L.check(getattr(L.lib(), name)(self.h, kind, int(rule), int(cur_rule), ntrials, L.ptr(so),
                                        L.ptr(bo), len(it), L.ptr(it), L.ptr(ns), L.ptr(nbc),
@@ -1272,6 +1363,119 @@ def cond_curve(lattice=0, m=50, n=50, pbc=0, kind=L.SITE, grid=(0.6, 0.7, 0.8, 0
             ctx.close()
         elif large:
             ctx.set_batch_large(was_large)
+
+
+def current_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.5, 0.6, 0.7, 0.8, 0.9), master=58302,
+                  numtrials=1, cur_rule=None, Va=1.0, g0=1.0, tol=1e-8, itmax=2500, cut=1e-6, batch=True,
+                  device_shuffle=False, ctx=None, device=0):
+    """Where the current flows as a function of p over trials: the backbone
+    fraction, the current moments and the current histogram of bond (grid a
+    list of pb), site (ps) or mixed (a list of (ps, pb)) percolation.  Trials
+    and counts are cond_curve's: trial ii draws shuffled_ids with
+    trial_seeds(master) (BOND: the bond order; SITE: the site order) or
+    paired_seeds(master) (SITEBOND), a grid point occupies the first
+    int(ps * t) sites and int(pb * nb) bonds.  batch=True on a lattice
+    batch_currents_supported accepts: all items of the call through
+    Context.batch_cond(currents=True) (device_shuffle=True: from the seeds);
+    batch=False, or another lattice: each item through occupy / label /
+    conductance(vint=True), conducting_bonds and current_stats_host.  Returns
+    (rows, records): records[ii][j] the item's dict (gtop, gbot, iter, nspan
+    and the current record's keys); rows[j], over the trials of point j that
+    span once or more (count `nspan`, accumulated in trial order), the means
+    G of gtop, backbone of nabove / nbonds, m2, m4, m6 of s_q / I^q and imax
+    of imax / I with I = gtop * Va, and the pooled hist (int64)."""
+    kind = int(kind)
+    if kind not in (L.BOND, L.SITE, L.SITEBOND):
+        raise ValueError("current_curve: kind BOND, SITE or SITEBOND")
+    if numtrials < 0:
+        raise ValueError("numtrials < 0")
+    mixed = kind == L.SITEBOND
+    need_s, need_b = kind != L.BOND, kind != L.SITE
+    rule = KIND_RULE[kind]
+    if cur_rule is None:
+        cur_rule = natural_cur_rule(kind)
+    own = ctx is None
+    ctx = ctx or Context(lattice, m, n, pbc, device)
+    try:
+        t, nb = ctx.t, ctx.nb
+        pts = [(float(p[0]), float(p[1])) if mixed else ((float(p), None) if need_s else (None, float(p)))
+               for p in grid]
+        npts = len(pts)
+        cnt_s = np.array([int(ps * t) for ps, _ in pts], np.int32) if need_s else None
+        cnt_b = np.array([int(pb * nb) for _, pb in pts], np.int32) if need_b else None
+        if mixed:
+            ss, bs = paired_seeds(master, max(numtrials, 1))
+        elif need_s:
+            ss, bs = trial_seeds(master, max(numtrials, 1)), None
+        else:
+            ss, bs = None, trial_seeds(master, max(numtrials, 1))
+        batched = bool(batch) and npts > 0 and numtrials > 0 and batch_currents_supported(
+            kind, ctx.lattice, ctx.m, ctx.n, ctx.pbc)
+        seeded = batched and device_shuffle and _device_shuffle_ok(ctx, kind)
+        keys = ("gtop", "gbot", "iter", "nspan")
+        if batched:
+            if seeded:
+                src = dict(site_seeds=ss[:numtrials] if need_s else None,
+                           bond_seeds=bs[:numtrials] if need_b else None)
+            else:
+                src = dict(site_orders=np.stack([shuffled_ids(t, int(ss[ii])) for ii in range(numtrials)])
+                           if need_s else None,
+                           bond_orders=np.stack([shuffled_ids(nb, int(bs[ii])) for ii in range(numtrials)])
+                           if need_b else None)
+            res = ctx.batch_cond(kind, np.repeat(np.arange(numtrials, dtype=np.int32), npts), **src,
+                                 item_nsites=np.tile(cnt_s, numtrials) if need_s else None,
+                                 item_nbonds=np.tile(cnt_b, numtrials) if need_b else None, cur_rule=cur_rule,
+                                 Va=Va, g0=g0, leak=LEAK, itol=2, tol=tol, itmax=itmax, currents=True, cut=cut)
+            res = [{k: r[k] for k in keys + L.CURRENTS_KEYS} for r in res]
+        else:
+            b1, b2 = bond_list(ctx.lattice, ctx.m, ctx.n, ctx.pbc)
+            res = []
+            for ii in range(numtrials):
+                so = shuffled_ids(t, int(ss[ii])) if need_s else None
+                bo = shuffled_ids(nb, int(bs[ii])) if need_b else None
+                for j in range(npts):
+                    ctx.occupy(kind, site_order=so, nsites=int(cnt_s[j]) if need_s else 0, bond_order=bo,
+                               nbonds_=int(cnt_b[j]) if need_b else 0)
+                    li = ctx.label(canon=True)
+                    c = ctx.conductance(rule, cur_rule, Va, g0, LEAK, 2, tol, itmax, vint=True)
+                    socc, bocc = ctx.occupancy()
+                    mask = conducting_bonds(kind, b1, b2, socc, bocc, li["canon"], li["span_root"])
+                    if c["status"] != 0:
+                        mask[:] = 0
+                    r = dict(gtop=c["gtop"], gbot=c["gbot"], iter=c["iter"], nspan=li["nspan"])
+                    r.update(current_stats_host(ctx.lattice, ctx.m, ctx.n, ctx.pbc, mask, c["vint"], Va, g0, cut))
+                    res.append(r)
+        records = [res[ii * npts:(ii + 1) * npts] for ii in range(numtrials)]
+        rows = []
+        for j, (ps, pb) in enumerate(pts):
+            acc = dict(nspan=0, G=0.0, backbone=0.0, m2=0.0, m4=0.0, m6=0.0, imax=0.0)
+            hist = np.zeros(64, dtype=np.int64)
+            for ii in range(numtrials):
+                r = records[ii][j]
+                if r["nspan"] < 1 or r["nbonds"] < 1:
+                    continue
+                cur = r["gtop"] * Va
+                i2 = cur * cur
+                acc["nspan"] += 1
+                acc["G"] += r["gtop"]
+                acc["backbone"] += r["nabove"] / r["nbonds"]
+                acc["m2"] += r["s2"] / i2
+                acc["m4"] += r["s4"] / (i2 * i2)
+                acc["m6"] += r["s6"] / (i2 * i2 * i2)
+                acc["imax"] += r["imax"] / cur
+                hist += r["hist"]
+            k = acc["nspan"]
+            row = {q: (v / k if k and q != "nspan" else v) for q, v in acc.items()}
+            if need_s:
+                row["ps"] = ps
+            if need_b:
+                row["pb"] = pb
+            row["hist"] = hist
+            rows.append(row)
+        return rows, records
+    finally:
+        if own:
+            ctx.close()
 
 
 def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5, 0.6, 0.7), master=58302,

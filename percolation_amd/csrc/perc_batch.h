@@ -4,10 +4,12 @@
 // dev_batch_run and k_batch_cond; perc_batch_large.hip and
 // perc_batch_weighted.hip their kernel and its launch; perc_batch_item.h the
 // device code the three kernels share (the item's front end, the workgroup
-// sums, the electrode rows' currents); perc_batch_scan.hip, perc_batch_clusters.hip
+// sums, the electrode rows' currents); perc_batch_currents.h the bond-current
+// epilogue of k_batch_cond's FIELDS instantiations; perc_batch_scan.hip, perc_batch_clusters.hip
 // and perc_batch_shuffle.hip their kernels and buffers; perc_batch_host.cpp the
 // C-ABI, the LDS plans and the ensemble's batched trial loop.
 #pragma once
+#include <cmath>
 #include <type_traits>
 
 #include "perc_internal.h"
@@ -112,11 +114,14 @@ bool batch_supported(const Geom& g, int kind = PERC_BOND);
 struct BatchWeights;
 hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank);
 hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s);
+// fld (optional): the launch is k_batch_cond's FIELDS instantiation, whatever
+// `large` says; it solves every item.
+struct BatchFields;
 hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_count, int solve, double Va,
                          double g0, double leak, int itol, double tol, int itmax, bool literal,
                          BatchOut* out, double* iout, bool large = false,
-                         const BatchWeights* wts = nullptr);
+                         const BatchWeights* wts = nullptr, const BatchFields* fld = nullptr);
 void dev_batch_free(perc_ctx* h);
 // host side (perc_batch_host.cpp): perc_batch_bondc's two halves, so the
 // ensemble uploads a group's orders once and launches over them many times.
@@ -142,7 +147,26 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
                          const int* item_nsites, const int* item_nbonds, int solve, bool replay,
                          double Va, double g0, double leak, int itol, double tol, int itmax,
                          perc_batch_item* out, const int* site_seeds = nullptr,
-                         const int* bond_seeds = nullptr, const BatchWeights* wts = nullptr);
+                         const int* bond_seeds = nullptr, const BatchWeights* wts = nullptr,
+                         const BatchFields* fld = nullptr);
+// ---- bond currents (perc_batch_currents.h: k_batch_cond's FIELDS epilogue) --
+// What perc_batch_cond_currents asks beside the conductances (host arrays, the
+// items' entries at the chunk's offset): the records (cur, one per item) and
+// the interior voltages (vint: items x N doubles, or NULL).  The default
+// kernel only: the large one keeps x on 2m rows, the weighted one has other
+// bond values.
+struct BatchFields {
+  double cut = 0.0;
+  perc_batch_currents* cur = nullptr;
+  double* vint = nullptr;
+};
+// octave of |i| below g0 Va (e0 = ilogb(g0 Va)): the record's histogram bin;
+// 63 for a zero current and for everything 63 octaves down or more
+__host__ __device__ inline int current_bin(int e0, double a) {
+  if (a == 0.0) return 63;
+  const long long b = (long long)e0 - (long long)ilogb(a);
+  return b < 0 ? 0 : (b > 63 ? 63 : (int)b);
+}
 // ---- lattices up to 128 x 128 (perc_batch_large.hip: k_batch_cond_large) --
 // One workgroup of 1024 threads, at most kBatchLargeEPT rows per thread: p
 // alone in LDS, every thread's row codes and r in its registers, q held in

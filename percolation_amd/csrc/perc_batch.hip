@@ -10,7 +10,7 @@
 // shared with k_batch_cond_large and k_batch_cond_w; this file keeps the
 // kernel's assembly and CG loop, the batch path's device buffers and
 // dev_batch_run, which fills the common argument block for all three.
-#include "perc_batch_item.h"
+#include "perc_batch_currents.h"
 
 namespace perc {
 namespace {
@@ -18,15 +18,26 @@ namespace {
 struct BatchArgs : BatchItemArgs {
   BatchLds L;
 };
+// ... of the FIELDS instantiations: the items' records, their interior
+// voltages (items x N, or NULL) and the backbone cut (device pointers)
+struct BatchFieldArgs : BatchArgs {
+  perc_batch_currents* cur;
+  double* vint;
+  double cut;
+};
 
 // NT threads, rows t, t + NT, .. (at most kBatchEPT) per thread.  LIT: the
 // literal dot order (wave 0 folds every sum in ascending j, fold_chunk) --
 // bitwise k_fold_init + k_cg_small<true, true>; else per thread in row
 // order, wave butterfly, waves in order.  KIND: PERC_BOND / PERC_SITE /
 // PERC_SITEBOND, with the kind's own conductance rule (the rules' numbers are
-// the kinds').
-template <int NT, bool LIT, int KIND>
-__global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
+// the kinds').  FIELDS: after the electrode currents, the item's bond-current
+// record (perc_batch_currents.h) and, where asked for, x itself -- an epilogue
+// over what the solve leaves in LDS: x in s_q (p is dead), the row codes, the
+// form table; the record's scratch is s_red.  The other instantiations take
+// BatchArgs and hold none of it.
+template <int NT, bool LIT, int KIND, bool FIELDS>
+__global__ __launch_bounds__(NT) void k_batch_cond(std::conditional_t<FIELDS, BatchFieldArgs, BatchArgs> a) {
   static_assert(PERC_RULE_BOND == PERC_BOND && PERC_RULE_SITE == PERC_SITE &&
                     PERC_RULE_MIXED == PERC_SITEBOND, "a kind's rule has its number");
   constexpr int RULE = KIND;
@@ -256,6 +267,14 @@ __global__ __launch_bounds__(NT) void k_batch_cond(BatchArgs a) {
     out->iter = k;
     out->err = err;
   }
+  if constexpr (FIELDS) {
+    if (a.vint) {  // (a kernel argument: uniform) x(i) as its owner left it in LDS, coalesced over t
+      double* v = a.vint + (size_t)item * N;
+#pragma unroll 1
+      for (int i = t; i < N; i += NT) v[i] = x[i];
+    }
+    batch_currents_record<NT>(N, x, s_c, s_off, s_red, g0, Va, a.cut, a.cur + item);
+  }
 }
 
 struct BatchState {
@@ -271,6 +290,11 @@ struct BatchState {
   size_t item_cap = 0, iout_cap = 0;
   int* d_sflag = nullptr;
   int lds_attr[3][2][3] = {};  // dynamic LDS granted per instantiation
+  int lds_attr_f[3][2][3] = {};  // ... of the FIELDS ones
+  // perc_batch_cond_currents: the launch's records and interior voltages
+  perc_batch_currents* d_cur = nullptr;
+  double* d_vint = nullptr;
+  size_t cur_cap = 0, vint_cap = 0;
   // perc_batch_cond_weighted: the chunk's explicit weight rows or its draws
   // (d_wsrc), the ConductCalc rows the kernel writes (d_wscr, items x nb), the
   // items' row numbers or seeds (d_wsel); perc_batch_twister's seeds and
@@ -307,6 +331,8 @@ void dev_batch_free(perc_ctx* h) {
   (void)hipFree(B->d_wsrc);
   (void)hipFree(B->d_wscr);
   (void)hipFree(B->d_wsel);
+  (void)hipFree(B->d_cur);
+  (void)hipFree(B->d_vint);
   delete B;
   h->batch = nullptr;
 }
@@ -375,7 +401,8 @@ hipError_t dev_batch_twister(perc_ctx* h, int nseeds, const unsigned* seeds, lon
 hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
                          const int* item_nsites, const int* item_count, int solve, double Va,
                          double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout, bool large, const BatchWeights* wts) {
+                         BatchOut* out, double* iout, bool large, const BatchWeights* wts,
+                         const BatchFields* fld) {
   if (nitems == 0) return hipSuccess;
   BatchState* B = batch_state(h);
   hipStream_t st = h->stream;
@@ -411,6 +438,14 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
                            hipMemcpyHostToDevice, st));
   // an item that stops before the currents leaves its iout row unwritten
   if (niout) HIP_TRY(hipMemsetAsync(B->d_iout, 0, sizeof(double) * niout, st));
+  // ... and its record and voltages: all zero
+  const size_t nvint = fld && fld->vint ? (size_t)nitems * (size_t)h->N : 0;
+  if (fld) {
+    HIP_TRY(grow(&B->d_cur, &B->cur_cap, (size_t)nitems));
+    HIP_TRY(grow(&B->d_vint, &B->vint_cap, nvint));
+    HIP_TRY(hipMemsetAsync(B->d_cur, 0, sizeof(perc_batch_currents) * nitems, st));
+    if (nvint) HIP_TRY(hipMemsetAsync(B->d_vint, 0, sizeof(double) * nvint, st));
+  }
   BatchItemArgs c;
   c.g = h->g;
   c.N = h->N;
@@ -436,7 +471,20 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
   c.leak = leak;
   c.tol = tol;
   hipError_t e;
-  if (wts) {  // k_batch_cond_w (perc_batch_weighted.hip): the common block and the weights
+  if (fld) {  // k_batch_cond's FIELDS instantiations: the common block, the plan and the fields
+    BatchFieldArgs a;
+    static_cast<BatchItemArgs&>(a) = c;
+    a.L = batch_lds(h->g, kind);
+    a.cur = B->d_cur;
+    a.vint = nvint ? B->d_vint : nullptr;
+    a.cut = fld->cut;
+    e = dispatch_threads(batch_threads(h->N), [&](auto nt, int slot) {
+      return dispatch_kind_order(kind, literal, [&](auto lit, auto kd) {
+        return launch_lds(&k_batch_cond<nt(), lit(), kd(), true>, &B->lds_attr_f[slot][lit()][kd()], a, nitems,
+                          nt(), st, "k_batch_cond");
+      });
+    });
+  } else if (wts) {  // k_batch_cond_w (perc_batch_weighted.hip): the common block and the weights
     const size_t nb = (size_t)c.nb;
     BatchWItems b;
     HIP_TRY(grow(&B->d_wsel, &B->wsel_cap, (size_t)nitems));
@@ -475,7 +523,7 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
     const BatchArgs a{c, batch_lds(h->g, kind)};
     e = dispatch_threads(batch_threads(h->N), [&](auto nt, int slot) {
       return dispatch_kind_order(kind, literal, [&](auto lit, auto kd) {
-        return launch_lds(&k_batch_cond<nt(), lit(), kd()>, &B->lds_attr[slot][lit()][kd()], a, nitems,
+        return launch_lds(&k_batch_cond<nt(), lit(), kd(), false>, &B->lds_attr[slot][lit()][kd()], a, nitems,
                           nt(), st, "k_batch_cond");
       });
     });
@@ -484,6 +532,10 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
   int flag = 0;
   HIP_TRY(hipMemcpyAsync(out, B->d_out, sizeof(BatchOut) * nitems, hipMemcpyDeviceToHost, st));
   if (niout) HIP_TRY(hipMemcpyAsync(iout, B->d_iout, sizeof(double) * niout, hipMemcpyDeviceToHost, st));
+  if (fld) {
+    HIP_TRY(hipMemcpyAsync(fld->cur, B->d_cur, sizeof(perc_batch_currents) * nitems, hipMemcpyDeviceToHost, st));
+    if (nvint) HIP_TRY(hipMemcpyAsync(fld->vint, B->d_vint, sizeof(double) * nvint, hipMemcpyDeviceToHost, st));
+  }
   HIP_TRY(hipMemcpyAsync(&flag, B->d_sflag, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (flag & 3) {  // a row without its stencil bond or form: perc_batch_supported excludes it

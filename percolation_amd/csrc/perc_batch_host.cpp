@@ -5,7 +5,9 @@
 // perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded, and the
 // weighted perc_batch_weighted_supported, perc_batch_cond_weighted,
 // perc_batch_twister, and the cluster tables' perc_batch_clusters_supported,
-// perc_batch_clusters, perc_batch_clusters_seeded):
+// perc_batch_clusters, perc_batch_clusters_seeded, and the current
+// distributions' perc_batch_currents_supported, perc_batch_cond_currents,
+// perc_batch_cond_currents_seeded, perc_current_stats_host):
 // argument checks, the orders' inverse permutations, the
 // launch geometry and LDS layouts, the fold of the terminal currents and the
 // single-path replay of the items several clusters span.
@@ -266,8 +268,9 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
                          const int* item_nsites, const int* item_nbonds, int solve, bool replay,
                          double Va, double g0, double leak, int itol, double tol, int itmax,
                          perc_batch_item* out, const int* site_seeds, const int* bond_seeds,
-                         const BatchWeights* wts) {
+                         const BatchWeights* wts, const BatchFields* fld) {
   const int nb = (int)h->nb, m = h->g.m, t = h->g.t;
+  const size_t N = (size_t)h->N;
   const int rule = kind;  // (PERC_RULE_* of a kind has the kind's number)
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
   const char* who = kind == PERC_BOND && cur_rule == PERC_CUR_FORTRAN ? "perc_batch_bondc" : "perc_batch_cond";
@@ -278,7 +281,13 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
   int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
   // ... and the weighted kernel's rows (its draws, its scratch: 8 nb bytes per item each)
   if (wts) chunk = std::max(1, std::min(chunk, (int)((64LL << 20) / (8LL * (nb + 16)))));
+  // ... and the interior voltages (8 N bytes per item)
+  if (fld && fld->vint) chunk = std::max(1, std::min(chunk, (int)((64LL << 20) / (16LL * m + 8LL * (long long)N))));
   std::vector<BatchOut> bo((size_t)std::min(nitems, chunk));
+  // a fallback item's record on the host: the bond list, the mask, the voltages
+  std::vector<int> fb1, fb2, canon;
+  std::vector<unsigned char> focc_s, focc_b, fmask;
+  std::vector<double> fvint;
   std::vector<double> iout(solve ? bo.size() * 2 * (size_t)m : 0);
   std::vector<int> slist, blist, sregen, bregen;
   for (int i0 = 0; i0 < nitems; i0 += chunk) {
@@ -289,9 +298,16 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
       if (wc.item_wset) wc.item_wset += i0;
       if (wc.item_wseed) wc.item_wseed += i0;
     }
+    BatchFields fc;
+    if (fld) {
+      fc = *fld;
+      fc.cur += i0;
+      if (fc.vint) fc.vint += (size_t)i0 * N;
+    }
     e = dev_batch_run(h, kind, cur_rule, n, item_trial + i0, need_s ? item_nsites + i0 : nullptr,
                       need_b ? item_nbonds + i0 : nullptr, solve ? 1 : 0, Va, g0, leak, itol, tol, itmax,
-                      literal, bo.data(), iout.data(), wts ? false : h->batch_large, wts ? &wc : nullptr);
+                      literal, bo.data(), iout.data(), wts || fld ? false : h->batch_large, wts ? &wc : nullptr,
+                      fld ? &fc : nullptr);
     if (e != hipSuccess) return hip_status(e, who);
     for (int i = 0; i < n; ++i) {
       perc_batch_item& it = out[i0 + i];
@@ -329,7 +345,8 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
         if (need_b && !occupy_prefix(bo, item_nbonds[i0 + i], nb, &blist, &bsrc, &blen)) return PERC_EINVAL;
         perc_label_info li{};
         int rc = perc_occupy(h, kind, slen, ssrc, blen, bsrc);
-        if (!rc) rc = perc_label(h, &li, nullptr);
+        if (fld) canon.resize((size_t)t);
+        if (!rc) rc = perc_label(h, &li, fld ? canon.data() : nullptr);
         if (rc) return rc;
         it.nclusters = li.nclusters;
         it.nspan = li.nspan;
@@ -343,7 +360,38 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
             rc = perc_set_bond_weights(h, wts->weights + (size_t)wts->item_wset[i0 + i] * nb, nb);
           else if (wts)
             rc = perc_set_conductcalc_weights(h, rule, wts->item_wseed[i0 + i]);
-          if (!rc) rc = perc_conductance(h, rule, cur_rule, Va, g0, leak, itol, tol, itmax, &res, nullptr);
+          double* vrow = nullptr;
+          if (fld) {
+            fvint.resize(N);
+            vrow = fld->vint ? fc.vint + (size_t)i * N : fvint.data();
+          }
+          if (!rc) rc = perc_conductance(h, rule, cur_rule, Va, g0, leak, itol, tol, itmax, &res, vrow);
+          if (!rc && fld && res.status == 0) {
+            // the conducting mask from the occupancy lists and the canonical
+            // labels (bond_value's three rules: a conducting bond's end sites
+            // share one cluster), then the host's record
+            if (fb1.empty()) {
+              fb1.resize((size_t)nb);
+              fb2.resize((size_t)nb);
+              perc_bond_list(h->g.lattice, m, h->g.n, h->g.pbc, fb1.data(), fb2.data());
+            }
+            focc_s.assign((size_t)t + 1, 0);
+            focc_b.assign((size_t)nb + 1, 0);
+            for (int k = 0; need_s && k < slen; ++k)
+              if (ssrc[k] >= 1 && ssrc[k] <= t) focc_s[ssrc[k]] = 1;
+            for (int k = 0; need_b && k < blen; ++k)
+              if (bsrc[k] >= 1 && bsrc[k] <= nb) focc_b[bsrc[k]] = 1;
+            fmask.assign((size_t)nb, 0);
+            for (int id = 1; id <= nb; ++id) {
+              const int s1 = fb1[id - 1], s2 = fb2[id - 1];
+              const bool occ = (!need_b || focc_b[id]) && (!need_s || (focc_s[s1] && focc_s[s2]));
+              fmask[id - 1] = occ && li.span_root > 0 && canon[s1 - 1] == li.span_root;
+            }
+            rc = perc_current_stats_host(h->g.lattice, m, h->g.n, h->g.pbc, fmask.data(), vrow, Va, g0, fld->cut,
+                                         &fc.cur[i]);
+          } else if (!rc && fld && fld->vint) {
+            std::fill(vrow, vrow + N, 0.0);
+          }
           if (wts) {
             const int rc2 = perc_set_bond_weights(h, nullptr, 0);
             if (!rc) rc = rc2;
@@ -471,7 +519,8 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
                            int ntrials, const int* site_src, const int* bond_src, int nitems,
                            const int* item_trial, const int* item_nsites, const int* item_nbonds,
                            int solve, double Va, double g0, double leak, int itol, double tol, int itmax,
-                           perc_batch_item* out, const BatchWeights* wts = nullptr) {
+                           perc_batch_item* out, const BatchWeights* wts = nullptr,
+                           const BatchFields* fld = nullptr) {
   if (!h) return PERC_EINVAL;
   auto bad = [who](const char* text) {
     set_error(std::string(who) + ": " + text);
@@ -488,7 +537,12 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
   if (ntrials < 0 || nitems < 0) return bad("ntrials or nitems < 0");
   if (itmax < 0) return bad("itmax < 0");
   if (solve && itol != 1 && itol != 2) return bad("itol 1 or 2 only");
-  if (wts) {  // its own kernel: the perc_set_batch_large flag is not read
+  if (fld) {  // the default kernel only: the perc_set_batch_large flag is not read
+    if (nitems && !fld->cur) return bad("cur missing");
+    if (!(fld->cut >= 0.0 && fld->cut <= 1.0)) return bad("cut outside [0, 1]");
+    if (!batch_supported(h->g, kind))
+      return bad("lattice not supported by the batch kernel for this kind (perc_batch_currents_supported)");
+  } else if (wts) {  // its own kernel: the perc_set_batch_large flag is not read
     if (!batch_w_supported(h->g, kind))
       return bad("lattice not supported by the weighted batch kernel for this kind "
                  "(perc_batch_weighted_supported)");
@@ -525,14 +579,14 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
     }
     return batch_run_items_kind(h, kind, cur_rule, nullptr, nullptr, nitems, item_trial, item_nsites,
                                 item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, site_src,
-                                bond_src, wts);
+                                bond_src, wts, fld);
   }
   int rc = need_b ? batch_upload_orders(h, ntrials, bond_src) : PERC_OK;
   if (!rc && need_s) rc = batch_upload_site_orders(h, ntrials, site_src);
   if (rc) return rc;
   return batch_run_items_kind(h, kind, cur_rule, site_src, bond_src, nitems, item_trial, item_nsites,
                               item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, nullptr, nullptr,
-                              wts);
+                              wts, fld);
 }
 
 int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, const int* site_orders,
@@ -552,6 +606,79 @@ int perc_batch_cond_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int nt
   return batch_cond_impl("perc_batch_cond_seeded", true, h, kind, rule, cur_rule, ntrials, site_seeds,
                          bond_seeds, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
                          itol, tol, itmax, out);
+}
+
+int perc_batch_currents_supported(int kind, int lattice, int m, int n, int pbc) {
+  return perc_batch_cond_supported(kind, lattice, m, n, pbc);
+}
+
+int perc_batch_cond_currents(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials,
+                             const int* site_orders, const int* bond_orders, int nitems,
+                             const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                             double Va, double g0, double leak, int itol, double tol, int itmax,
+                             perc_batch_item* out, double cut, perc_batch_currents* cur, double* vint_out) {
+  BatchFields fld;
+  fld.cut = cut;
+  fld.cur = cur;
+  fld.vint = vint_out;
+  return batch_cond_impl("perc_batch_cond_currents", false, h, kind, rule, cur_rule, ntrials, site_orders,
+                         bond_orders, nitems, item_trial, item_nsites, item_nbonds, 1, Va, g0, leak, itol, tol,
+                         itmax, out, nullptr, &fld);
+}
+
+int perc_batch_cond_currents_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials,
+                                    const int* site_seeds, const int* bond_seeds, int nitems,
+                                    const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                                    double Va, double g0, double leak, int itol, double tol, int itmax,
+                                    perc_batch_item* out, double cut, perc_batch_currents* cur,
+                                    double* vint_out) {
+  BatchFields fld;
+  fld.cut = cut;
+  fld.cur = cur;
+  fld.vint = vint_out;
+  return batch_cond_impl("perc_batch_cond_currents_seeded", true, h, kind, rule, cur_rule, ntrials, site_seeds,
+                         bond_seeds, nitems, item_trial, item_nsites, item_nbonds, 1, Va, g0, leak, itol, tol,
+                         itmax, out, nullptr, &fld);
+}
+
+int perc_current_stats_host(int lattice, int m, int n, int pbc, const unsigned char* conducting,
+                            const double* vint, double Va, double g0, double cut, perc_batch_currents* out) {
+  auto bad = [](const char* text) {
+    set_error(std::string("perc_current_stats_host: ") + text);
+    return PERC_EINVAL;
+  };
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return bad("lattice PERC_SQUARE or PERC_TRIANGULAR only");
+  if (m < 1 || n < 1 || (long long)m * n >= (1LL << 31) - 16) return bad("m or n < 1, or m * n too large");
+  if (!conducting || !vint || !out) return bad("conducting, vint or out missing");
+  if (!(cut >= 0.0 && cut <= 1.0)) return bad("cut outside [0, 1]");
+  const int t = m * n, nb = perc_nbonds(lattice, m, n, pbc);
+  std::vector<int> b1((size_t)std::max(nb, 1)), b2((size_t)std::max(nb, 1));
+  if (perc_bond_list(lattice, m, n, pbc, b1.data(), b2.data()) != nb) return bad("the bond list");
+  std::memset(out, 0, sizeof(*out));
+  auto interior = [&](int s) { return s > m && s <= t - m; };
+  auto V = [&](int s) { return s <= m ? 0.0 : (s > t - m ? Va : vint[s - m - 1]); };
+  auto each = [&](auto f) {  // |i| of every counted bond, in id order
+    for (int k = 0; k < nb; ++k) {
+      if (!conducting[k] || !(interior(b1[k]) || interior(b2[k]))) continue;
+      const double d = V(b2[k]) - V(b1[k]);
+      const double ib = g0 * d;
+      f(std::fabs(ib));
+    }
+  };
+  const int e0 = ilogb(g0 * Va);
+  each([&](double a) {
+    const double i2 = a * a, i4 = i2 * i2, i6 = i4 * i2;
+    ++out->nbonds;
+    out->imax = std::fmax(out->imax, a);
+    out->s1 = out->s1 + a;
+    out->s2 = out->s2 + i2;
+    out->s4 = out->s4 + i4;
+    out->s6 = out->s6 + i6;
+    ++out->hist[current_bin(e0, a)];
+  });
+  const double thr = cut * out->imax;
+  each([&](double a) { out->nabove += a >= thr ? 1 : 0; });
+  return PERC_OK;
 }
 
 int perc_batch_weighted_supported(int kind, int lattice, int m, int n, int pbc) {

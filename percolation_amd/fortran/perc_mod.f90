@@ -382,6 +382,47 @@ module perc_api
       real(c_double), value :: Va, g0, leak, tol
     end function perc_batch_cond_seeded
 
+    ! host-only: exactly perc_batch_cond_supported
+    integer(c_int) function perc_batch_currents_supported(kind, lattice, m, n, pbc) &
+        bind(C, name='perc_batch_currents_supported')
+      import :: c_int
+      integer(c_int), value :: kind, lattice, m, n, pbc
+    end function perc_batch_currents_supported
+
+    ! perc_batch_cond (always solving) with the bond-current record of every
+    ! item (cur: perc_batch_currents records, 304 bytes each) and, unless
+    ! c_null_ptr, the interior voltages (vint_out: nitems x N doubles)
+    integer(c_int) function perc_batch_cond_currents(h, kind, rule, cur_rule, ntrials, site_orders, &
+        bond_orders, nitems, item_trial, item_nsites, item_nbonds, Va, g0, leak, itol, tol, itmax, &
+        out, cut, cur, vint_out) bind(C, name='perc_batch_cond_currents')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h, site_orders, bond_orders, item_trial, item_nsites, item_nbonds, out
+      type(c_ptr), value :: cur, vint_out
+      integer(c_int), value :: kind, rule, cur_rule, ntrials, nitems, itol, itmax
+      real(c_double), value :: Va, g0, leak, tol, cut
+    end function perc_batch_cond_currents
+
+    ! the same with one seed per trial in place of the order lists
+    integer(c_int) function perc_batch_cond_currents_seeded(h, kind, rule, cur_rule, ntrials, &
+        site_seeds, bond_seeds, nitems, item_trial, item_nsites, item_nbonds, Va, g0, leak, itol, &
+        tol, itmax, out, cut, cur, vint_out) bind(C, name='perc_batch_cond_currents_seeded')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h, site_seeds, bond_seeds, item_trial, item_nsites, item_nbonds, out
+      type(c_ptr), value :: cur, vint_out
+      integer(c_int), value :: kind, rule, cur_rule, ntrials, nitems, itol, itmax
+      real(c_double), value :: Va, g0, leak, tol, cut
+    end function perc_batch_cond_currents_seeded
+
+    ! the record of one realisation on the host: conducting (nb bytes, by bond
+    ! id), vint (t - 2m doubles), out (one perc_batch_currents record)
+    integer(c_int) function perc_current_stats_host(lattice, m, n, pbc, conducting, vint, Va, g0, &
+        cut, out) bind(C, name='perc_current_stats_host')
+      import :: c_int, c_ptr, c_double
+      integer(c_int), value :: lattice, m, n, pbc
+      type(c_ptr), value :: conducting, vint, out
+      real(c_double), value :: Va, g0, cut
+    end function perc_current_stats_host
+
     ! host-only: 1 when the weighted batch kernel can run this kind on this lattice
     integer(c_int) function perc_batch_weighted_supported(kind, lattice, m, n, pbc) &
         bind(C, name='perc_batch_weighted_supported')

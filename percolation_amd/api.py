@@ -537,6 +537,46 @@ class Context:
         L.check(L.lib().perc_system_size(self.h, out), "perc_system_size")
         return int(out[0]), int(out[1])
 
+    def _trial_lists(self, site_orders, bond_orders, site_seeds, bond_seeds):
+        """The order lists (ntrials, N + 1) or seed lists (ntrials) of a batch
+        call as libperc takes them: (so, bo, ntrials, seeded); ntrials None
+        where no list is given."""
+        so = bo = ntrials = None
+        seeded = site_seeds is not None or bond_seeds is not None
+        if seeded and (site_orders is not None or bond_orders is not None):
+            raise ValueError("orders or seeds, not both")
+        if site_seeds is not None:
+            so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
+            ntrials = len(so)
+        if bond_seeds is not None:
+            bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
+            if ntrials is not None and len(bo) != ntrials:
+                raise ValueError("site_seeds and bond_seeds differ in trials")
+            ntrials = len(bo)
+        if site_orders is not None:
+            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
+            ntrials = so.shape[0]
+        if bond_orders is not None:
+            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
+            if ntrials is not None and bo.shape[0] != ntrials:
+                raise ValueError("site_orders and bond_orders differ in trials")
+            ntrials = bo.shape[0]
+        return so, bo, ntrials, seeded
+
+    @staticmethod
+    def _item_lists(item_trial, item_nsites, item_nbonds):
+        """The items of a batch call as libperc takes them: (it, ns, nbc)."""
+        it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
+        ns = nbc = None
+        if item_nsites is not None:
+            ns = np.ascontiguousarray(item_nsites, dtype=np.int32).reshape(-1)
+        if item_nbonds is not None:
+            nbc = np.ascontiguousarray(item_nbonds, dtype=np.int32).reshape(-1)
+        for c in (ns, nbc):
+            if c is not None and c.shape != it.shape:
+                raise ValueError("item_trial and the count lists differ in length")
+        return it, ns, nbc
+
     def batch_bondc(self, orders, item_trial, item_count, solve=True, Va=1.0, g0=1.0, leak=LEAK,
                     itol=2, tol=1e-8, itmax=2500):
         """perc_batch_bondc: many small bond realisations in one launch, one
@@ -623,37 +663,10 @@ class Context:
         if cur_rule is None:
             cur_rule = natural_cur_rule(kind)
         it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
-        so = bo = ns = nbc = None
-        ntrials = None
-        seeded = site_seeds is not None or bond_seeds is not None
-        if seeded:
-            if site_orders is not None or bond_orders is not None:
-                raise ValueError("orders or seeds, not both")
-            if site_seeds is not None:
-                so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
-                ntrials = len(so)
-            if bond_seeds is not None:
-                bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
-                if ntrials is not None and len(bo) != ntrials:
-                    raise ValueError("site_seeds and bond_seeds differ in trials")
-                ntrials = len(bo)
-        if site_orders is not None:
-            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
-            ntrials = so.shape[0]
-        if bond_orders is not None:
-            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
-            if ntrials is not None and bo.shape[0] != ntrials:
-                raise ValueError("site_orders and bond_orders differ in trials")
-            ntrials = bo.shape[0]
+        so, bo, ntrials, seeded = self._trial_lists(site_orders, bond_orders, site_seeds, bond_seeds)
         if ntrials is None:
             ntrials = int(it.max()) + 1 if len(it) else 0  # (no list at all: libperc reports it)
-        if item_nsites is not None:
-            ns = np.ascontiguousarray(item_nsites, dtype=np.int32).reshape(-1)
-        if item_nbonds is not None:
-            nbc = np.ascontiguousarray(item_nbonds, dtype=np.int32).reshape(-1)
-        for c in (ns, nbc):
-            if c is not None and c.shape != it.shape:
-                raise ValueError("item_trial and the count lists differ in length")
+        it, ns, nbc = self._item_lists(it, item_nsites, item_nbonds)
         out = (L.BatchItem * max(len(it), 1))()
         if weights is not None or item_wset is not None or item_wseed is not None:
             if seeded:
@@ -729,24 +742,8 @@ class Context:
         return self._batch_scan(kind, None, None, scan, fixed, site_seeds, bond_seeds, True)
 
     def _batch_scan(self, kind, site_orders, bond_orders, scan, fixed, site_seeds, bond_seeds, seeded):
-        so = bo = fx = None
-        ntrials = None
-        if site_seeds is not None:
-            so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
-            ntrials = len(so)
-        if bond_seeds is not None:
-            bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
-            if ntrials is not None and len(bo) != ntrials:
-                raise ValueError("site_seeds and bond_seeds differ in trials")
-            ntrials = len(bo)
-        if site_orders is not None:
-            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
-            ntrials = so.shape[0]
-        if bond_orders is not None:
-            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
-            if ntrials is not None and bo.shape[0] != ntrials:
-                raise ValueError("site_orders and bond_orders differ in trials")
-            ntrials = bo.shape[0]
+        fx = None
+        so, bo, ntrials, _ = self._trial_lists(site_orders, bond_orders, site_seeds, bond_seeds)
         if fixed is not None:
             fx = np.ascontiguousarray(fixed, dtype=np.int32).reshape(-1)
             if ntrials is not None and len(fx) == 1:
@@ -776,37 +773,10 @@ class Context:
         shuffled on the device -- the same records."""
         kind, nexact = int(kind), int(nexact)
         it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
-        so = bo = ns = nbc = None
-        ntrials = None
-        seeded = site_seeds is not None or bond_seeds is not None
-        if seeded:
-            if site_orders is not None or bond_orders is not None:
-                raise ValueError("orders or seeds, not both")
-            if site_seeds is not None:
-                so = np.ascontiguousarray(site_seeds, dtype=np.int32).reshape(-1)
-                ntrials = len(so)
-            if bond_seeds is not None:
-                bo = np.ascontiguousarray(bond_seeds, dtype=np.int32).reshape(-1)
-                if ntrials is not None and len(bo) != ntrials:
-                    raise ValueError("site_seeds and bond_seeds differ in trials")
-                ntrials = len(bo)
-        if site_orders is not None:
-            so = np.ascontiguousarray(site_orders, dtype=np.int32).reshape(-1, self.t + 1)
-            ntrials = so.shape[0]
-        if bond_orders is not None:
-            bo = np.ascontiguousarray(bond_orders, dtype=np.int32).reshape(-1, self.nb + 1)
-            if ntrials is not None and bo.shape[0] != ntrials:
-                raise ValueError("site_orders and bond_orders differ in trials")
-            ntrials = bo.shape[0]
+        so, bo, ntrials, seeded = self._trial_lists(site_orders, bond_orders, site_seeds, bond_seeds)
         if ntrials is None:
             ntrials = int(it.max()) + 1 if len(it) else 0  # (no list at all: libperc reports it)
-        if item_nsites is not None:
-            ns = np.ascontiguousarray(item_nsites, dtype=np.int32).reshape(-1)
-        if item_nbonds is not None:
-            nbc = np.ascontiguousarray(item_nbonds, dtype=np.int32).reshape(-1)
-        for c in (ns, nbc):
-            if c is not None and c.shape != it.shape:
-                raise ValueError("item_trial and the count lists differ in length")
+        it, ns, nbc = self._item_lists(it, item_nsites, item_nbonds)
         out = np.zeros(max(len(it), 1), dtype=L.CLUSTER_DTYPE)
         hrows = np.zeros((max(len(it), 1), max(nexact, 0) + 32), dtype=np.int32) if hist else None
         name = "perc_batch_clusters_seeded" if seeded else "perc_batch_clusters"

@@ -1,13 +1,17 @@
 // perc_batch.h -- the batch path of libperc: many independent small
 // realisations (bond, site or mixed) in one launch, one workgroup per
-// (trial, counts) item.  Who owns what: perc_batch.hip the device buffers,
-// dev_batch_run and k_batch_cond; perc_batch_large.hip and
-// perc_batch_weighted.hip their kernel and its launch; perc_batch_item.h the
-// device code the three kernels share (the item's front end, the workgroup
-// sums, the electrode rows' currents); perc_batch_currents.h the bond-current
-// epilogue of k_batch_cond's FIELDS instantiations; perc_batch_scan.hip, perc_batch_clusters.hip
-// and perc_batch_shuffle.hip their kernels and buffers; perc_batch_host.cpp the
-// C-ABI, the LDS plans and the ensemble's batched trial loop.
+// (trial, counts) item.  Who owns what: perc_batch.hip the context's rank
+// store (below), the conductance path's device buffers, dev_batch_run and
+// k_batch_cond; perc_batch_large.hip and perc_batch_weighted.hip their kernel
+// and its launch; perc_batch_item.h the device code the three kernels share
+// (the item's front end, the workgroup sums, the electrode rows' currents);
+// perc_batch_currents.h the bond-current epilogue of k_batch_cond's FIELDS
+// instantiations; perc_batch_scan.hip, perc_batch_clusters.hip and
+// perc_batch_shuffle.hip their kernels and per-launch buffers (ranks in device
+// memory in, results out); perc_batch_plan.h the host-only plan (the orders'
+// inverse permutations, the item checks, the cut of a call into runs);
+// perc_batch_host.cpp the C-ABI, the LDS plans and the one front door of the
+// conductance, scan and cluster calls.
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -102,53 +106,84 @@ int batch_threads(int N);
 // kind's own LDS layout)
 bool batch_supported(const Geom& g, int kind = PERC_BOND);
 
-// device side (perc_batch.hip).  The orders' inverse permutations, once per
-// group of trials: rank[tr * nb + id - 1] = position of bond id in trial
-// tr's order (INT_MAX: not in it); then any number of launches over items of
-// those trials.  out[nitems]; iout[nitems * 2m] (solve != 0 only).  The
-// site ranks (rank_s[tr * t + s - 1]) go beside them for the site and mixed
-// kinds; dev_batch_run reads the arrays its kind needs (item_nsites /
-// item_count may be NULL where the kind does not read them) and refuses an
-// item whose trial lies outside them.  wts (optional): the items' per-bond
-// weights -- the launch is k_batch_cond_w's, whatever `large` says.
+// ---- the rank store (perc_batch.hip) -------------------------------------
+// One per context: for each list (PERC_BOND: ntrials x nb, PERC_SITE: ntrials
+// x t) the trials' rank arrays in device memory -- rank[tr * N + id - 1] =
+// position of id in trial tr's order (INT_MAX: not in it) -- and one pinned
+// host row to form them in.  Every batch kernel reads its ranks from here.
+// The contract: every C-ABI batch call leaves the store holding the trials of
+// its last run, numbered as that run numbered them, so nothing may rely on
+// ranks surviving across C-ABI calls.  The one user of several launches over
+// one filling is the ensemble's batched trial loop, which makes no C-ABI call
+// in between: batch_upload_orders -> batch_run_items -> batch_scan_uploaded
+// -> batch_run_items.
+// stage: the list's pinned row sized for ntrials trials (the contents are not
+// kept); commit: the row's first ntrials trials copied up on the context's
+// stream and marked as held (the row is the store's until the next stage)
+hipError_t dev_batch_stage(perc_ctx* h, int list, int ntrials, int** row);
+hipError_t dev_batch_commit(perc_ctx* h, int list, int ntrials);
+// the list's device buffer sized for ntrials trials and marked as holding
+// them, for a kernel to fill (the device shuffle)
+hipError_t dev_batch_reserve(perc_ctx* h, int list, int ntrials, int** d_rank);
+// the list's ranks in device memory and the trials they hold (NULL, 0: none)
+const int* dev_batch_ranks(perc_ctx* h, int list, int* ntrials);
+// ---- conductance (perc_batch.hip: dev_batch_run) -------------------------
+// the solve's parameters, as perc_batch_cond takes them; literal: the dot order
+struct BatchSolve {
+  int solve = 1, cur_rule = PERC_CUR_FORTRAN;
+  double Va = 1.0, g0 = 1.0, leak = 0.0;
+  int itol = 2;
+  double tol = 0.0;
+  int itmax = 0;
+  bool literal = false;
+};
+// One launch over nitems items of the trials the store holds: out[nitems];
+// iout[nitems * 2m] (solve != 0 only).  It reads the rank arrays its kind
+// needs (item_nsites / item_count may be NULL where the kind does not read
+// them) and refuses an item whose trial lies outside them.  wts (optional):
+// the items' per-bond weights -- the launch is k_batch_cond_w's, whatever
+// `large` says.  fld (optional): the launch is k_batch_cond's FIELDS
+// instantiation, whatever `large` says; it solves every item.
 struct BatchWeights;
-hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank);
-hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s);
-// fld (optional): the launch is k_batch_cond's FIELDS instantiation, whatever
-// `large` says; it solves every item.
 struct BatchFields;
-hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
-                         const int* item_nsites, const int* item_count, int solve, double Va,
-                         double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout, bool large = false,
-                         const BatchWeights* wts = nullptr, const BatchFields* fld = nullptr);
+hipError_t dev_batch_run(perc_ctx* h, int kind, const BatchSolve& sv, int nitems, const int* item_trial,
+                         const int* item_nsites, const int* item_count, BatchOut* out, double* iout,
+                         bool large = false, const BatchWeights* wts = nullptr,
+                         const BatchFields* fld = nullptr);
 void dev_batch_free(perc_ctx* h);
-// host side (perc_batch_host.cpp): perc_batch_bondc's two halves, so the
-// ensemble uploads a group's orders once and launches over them many times.
-// replay: run the items several clusters span through the single path
-// (false: leave them with fallback = 1 and the kernel's nspan -- enough for
-// the bisection of the first spanning count)
+// host side (perc_batch_host.cpp).  Where a call's ranks come from: order
+// lists (ntrials x (t + 1) / ntrials x (nb + 1)) or, seeded, one seed per
+// trial for the device shuffle; a list the kind does not read may be NULL.
+// held: the store already holds the call's trials under the caller's numbers
+// (batch_upload_orders), nothing is staged or shuffled.  replay: run the
+// items several clusters span through the single path (false: leave them with
+// fallback = 1 and the kernel's nspan -- enough for the bisection of the first
+// spanning count); a replayed item's order is the caller's trial's, or,
+// seeded, regenerated with perc_shuffle_seeded.
+struct BatchSources {
+  bool seeded = false;
+  const int* site_src = nullptr;
+  const int* bond_src = nullptr;
+  bool held = false;
+  bool replay = true;
+};
+// The items of a conductance call of any kind in runs of bounded size: per
+// run, the ranks of the trials it names into the store (unless held), one
+// launch, the fold of the terminal currents, the replays.  wts (optional):
+// the call's per-bond weights (perc_batch_cond_weighted) -- k_batch_cond_w's
+// launches, and a replayed item's weights set on the context after its
+// labeling and cleared after it.
+int batch_run_items_kind(perc_ctx* h, int kind, int ntrials, const BatchSources& src, int nitems,
+                         const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                         const BatchSolve& sv, perc_batch_item* out, const BatchWeights* wts = nullptr,
+                         const BatchFields* fld = nullptr);
+// perc_batch_bondc's two halves, so the ensemble fills the store with a
+// group's orders once and launches over them many times (the bond kind under
+// PERC_CUR_FORTRAN, the store held)
 int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders);
 int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
                     const int* item_count, int solve, bool replay, double Va, double g0, double leak,
                     int itol, double tol, int itmax, perc_batch_item* out);
-// the same for any kind (batch_run_items is its bond kind under
-// PERC_CUR_FORTRAN): site_orders / item_nsites and bond_orders / item_nbonds
-// as perc_batch_cond takes them, the orders uploaded by batch_upload_orders /
-// batch_upload_site_orders
-int batch_upload_site_orders(perc_ctx* h, int ntrials, const int* site_orders);
-// A NULL order list the kind reads stands for its seeds (perc_batch_cond_seeded:
-// the ranks came from dev_shuffle_run): the replay regenerates that trial's
-// order with perc_shuffle_seeded.  wts (optional): the call's per-bond weights
-// (perc_batch_cond_weighted) -- k_batch_cond_w's launches, and a replayed
-// item's weights set on the context after its labeling and cleared after it.
-int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_orders,
-                         const int* bond_orders, int nitems, const int* item_trial,
-                         const int* item_nsites, const int* item_nbonds, int solve, bool replay,
-                         double Va, double g0, double leak, int itol, double tol, int itmax,
-                         perc_batch_item* out, const int* site_seeds = nullptr,
-                         const int* bond_seeds = nullptr, const BatchWeights* wts = nullptr,
-                         const BatchFields* fld = nullptr);
 // ---- bond currents (perc_batch_currents.h: k_batch_cond's FIELDS epilogue) --
 // What perc_batch_cond_currents asks beside the conductances (host arrays, the
 // items' entries at the chunk's offset): the records (cur, one per item) and
@@ -266,21 +301,13 @@ int scan_threads(int t);
 // host-only check of perc_scan_supported
 bool scan_supported(const Geom& g);
 // device side.  Scan of ntrials trials from rank arrays in device memory
-// (d_rank_b: ntrials x nb as dev_batch_upload leaves them, d_rank_s: ntrials
-// x t; either may be NULL where the kind does not read it); fixed (host,
-// ntrials, mixed kinds only); out (host, ntrials).  kind PERC_BOND /
-// PERC_SITE / PERC_SITEBOND, scan PERC_BOND / PERC_SITE (mixed only).
+// (the store's: d_rank_b ntrials x nb, d_rank_s ntrials x t; either may be
+// NULL where the kind does not read it); fixed (host, ntrials, mixed kinds
+// only); out (host, ntrials).  kind PERC_BOND / PERC_SITE / PERC_SITEBOND,
+// scan PERC_BOND / PERC_SITE (mixed only).
 hipError_t dev_scan_run(perc_ctx* h, int kind, int scan, int ntrials, const int* d_rank_s,
                         const int* d_rank_b, const int* fixed, perc_scan_item* out);
-// rank arrays of perc_batch_scan's own orders (host, ntrials x t / ntrials x
-// nb, either NULL) uploaded into the scan's buffers, then dev_scan_run
-hipError_t dev_scan_upload_run(perc_ctx* h, int kind, int scan, int ntrials, const int* rank_s,
-                               const int* rank_b, const int* fixed, perc_scan_item* out);
 void dev_scan_free(perc_ctx* h);
-// the rank arrays dev_batch_upload left on the device (NULL before one)
-const int* dev_batch_ranks(perc_ctx* h, int* ntrials);
-// the same for the site ranks dev_batch_upload_sites left
-const int* dev_batch_site_ranks(perc_ctx* h, int* ntrials);
 // ---- cluster statistics (perc_batch_clusters.hip: k_batch_clusters) -----
 // the exact part of an item's histogram row: sizes 1..nexact, nexact at most
 constexpr int kClusterExactMax = 1024;
@@ -304,14 +331,6 @@ bool clusters_supported(const Geom& g, int nexact);
 hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank_s, const int* d_rank_b,
                             const int* item_trial, const int* item_nsites, const int* item_nbonds,
                             int nexact, perc_cluster_item* out, int* hist);
-// pinned host arrays of ns / nbk ints (either may be 0: NULL) for the call to
-// form a launch's rank arrays in; they live with the kernel's buffers
-hipError_t dev_clusters_stage(perc_ctx* h, size_t ns, size_t nbk, int** rank_s, int** rank_b);
-// rank arrays of the call's own orders (host, ntrials x t / ntrials x nb,
-// either NULL) uploaded into the kernel's buffers, then dev_clusters_run
-hipError_t dev_clusters_upload_run(perc_ctx* h, int kind, int ntrials, const int* rank_s, const int* rank_b,
-                                   int nitems, const int* item_trial, const int* item_nsites,
-                                   const int* item_nbonds, int nexact, perc_cluster_item* out, int* hist);
 void dev_clusters_free(perc_ctx* h);
 // ---- device shuffle (perc_batch_shuffle.hip: k_shuffle_ranks) -----------
 // Byte offsets of k_shuffle_ranks' LDS arena (every offset a multiple of 16):
@@ -323,22 +342,18 @@ ShuffleLds shuffle_lds(int N);
 // host-only check of perc_shuffle_device_supported: every id of 1..N and the
 // spill slot in 16 bits, the arena within a workgroup's LDS
 bool shuffle_supported(int N);
-// The bond (list PERC_BOND, ntrials x nb) or site (PERC_SITE, ntrials x t)
-// rank buffer of the batch path sized for ntrials trials and marked as
-// holding them, for a kernel to fill: what dev_batch_upload /
-// dev_batch_upload_sites do, without the copy.
-hipError_t dev_batch_reserve(perc_ctx* h, int list, int ntrials, int** d_rank);
-// ntrials trials of that list shuffled by seeds (host) into the reserved
-// buffer; orders_out (host, ntrials x (N + 1)) and ranks_out (host, ntrials x
-// N) may be NULL.  list kShuffleFree: a list of nfree ids that is no list of
-// the lattice, its ranks in a buffer of the shuffle's own (the batch rank
-// buffers stay as they are).
+// ntrials trials of a list (PERC_BOND / PERC_SITE) shuffled by seeds (host)
+// into the rank store (dev_batch_reserve); orders_out (host, ntrials x
+// (N + 1)) and ranks_out (host, ntrials x N) may be NULL.  list kShuffleFree:
+// a list of nfree ids that is no list of the lattice, its ranks in a buffer of
+// the shuffle's own (the rank store stays as it is).
 constexpr int kShuffleFree = -1;
 hipError_t dev_shuffle_run(perc_ctx* h, int list, int ntrials, const int* seeds, int* orders_out,
                            int* ranks_out, int nfree = 0);
 void dev_shuffle_free(perc_ctx* h);
 // host side (perc_batch_host.cpp): the first spanning bond count of every
-// trial of the group batch_upload_orders uploaded (bond kind), one launch
+// trial of the group batch_upload_orders left in the store (bond kind), one
+// launch
 int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out);
 // the closed-form rows' forms of the square lattice (perc_assemble.hip)
 void asm_closed_forms(perc_ctx* h, int* fast_out, int* fl_out, int* fr_out);

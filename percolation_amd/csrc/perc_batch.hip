@@ -277,17 +277,25 @@ __global__ __launch_bounds__(NT) void k_batch_cond(std::conditional_t<FIELDS, Ba
   }
 }
 
+// The context's one rank store: per list (0: bonds, ntrials x nb; 1: sites,
+// ntrials x t) the ranks in device memory with the trials they hold, and the
+// pinned host row a call forms them in (a fresh pageable array of a launch's
+// 64 MB costs more in page faults and the runtime's staged copy than the
+// kernels run).  perc_batch.h states its contract.
+struct RankStore {
+  int* d_rank[2] = {};
+  size_t cap[2] = {};
+  int held[2] = {};
+  int* h_row[2] = {};
+  size_t hcap[2] = {};
+  bool in_flight[2] = {};  // a commit's copy may still read h_row
+};
+
 struct BatchState {
-  int* d_rank = nullptr;  // bond ranks, ntrials x nb
-  size_t rank_cap = 0;
-  int ntrials = 0;
-  int* d_rank_s = nullptr;  // site ranks, ntrials_s x t
-  size_t rank_s_cap = 0;
-  int ntrials_s = 0;
-  int* d_items = nullptr;  // item_trial, then item_count, then item_nsites
-  BatchOut* d_out = nullptr;
+  RankStore ranks;
+  ItemLists<BatchOut, 3> items;  // item_trial, then item_count, then item_nsites
   double* d_iout = nullptr;
-  size_t item_cap = 0, iout_cap = 0;
+  size_t iout_cap = 0;
   int* d_sflag = nullptr;
   int lds_attr[3][2][3] = {};  // dynamic LDS granted per instantiation
   int lds_attr_f[3][2][3] = {};  // ... of the FIELDS ones
@@ -305,13 +313,6 @@ struct BatchState {
   size_t wsrc_cap = 0, wscr_cap = 0, wsel_cap = 0;
 };
 
-// a rank array of n ints in *p (capacity *cap), copied from the host
-hipError_t upload_ranks(int** p, size_t* cap, size_t n, const int* rank, hipStream_t st) {
-  HIP_TRY(grow(p, cap, n));
-  if (n) HIP_TRY(hipMemcpyAsync(*p, rank, sizeof(int) * n, hipMemcpyHostToDevice, st));
-  return hipStreamSynchronize(st);  // (the caller's array may go away)
-}
-
 }  // namespace
 
 static BatchState* batch_state(perc_ctx* h) {
@@ -322,10 +323,11 @@ static BatchState* batch_state(perc_ctx* h) {
 void dev_batch_free(perc_ctx* h) {
   BatchState* B = static_cast<BatchState*>(h->batch);
   if (!B) return;
-  (void)hipFree(B->d_rank);
-  (void)hipFree(B->d_rank_s);
-  (void)hipFree(B->d_items);
-  (void)hipFree(B->d_out);
+  for (int l = 0; l < 2; ++l) {
+    (void)hipFree(B->ranks.d_rank[l]);
+    if (B->ranks.h_row[l]) (void)hipHostFree(B->ranks.h_row[l]);
+  }
+  B->items.release();
   (void)hipFree(B->d_iout);
   (void)hipFree(B->d_sflag);
   (void)hipFree(B->d_wsrc);
@@ -337,45 +339,46 @@ void dev_batch_free(perc_ctx* h) {
   h->batch = nullptr;
 }
 
-const int* dev_batch_ranks(perc_ctx* h, int* ntrials) {
-  BatchState* B = static_cast<BatchState*>(h->batch);
-  *ntrials = B ? B->ntrials : 0;
-  return B ? B->d_rank : nullptr;
-}
+// a list's slot in the store, and the ints of one trial of it
+static int rank_slot(int list) { return list == PERC_BOND ? 0 : 1; }
+static size_t rank_len(perc_ctx* h, int list) { return (size_t)(list == PERC_BOND ? h->nb : h->g.t); }
 
-const int* dev_batch_site_ranks(perc_ctx* h, int* ntrials) {
+const int* dev_batch_ranks(perc_ctx* h, int list, int* ntrials) {
   BatchState* B = static_cast<BatchState*>(h->batch);
-  *ntrials = B ? B->ntrials_s : 0;
-  return B ? B->d_rank_s : nullptr;
+  const int l = rank_slot(list);
+  *ntrials = B && B->ranks.d_rank[l] ? B->ranks.held[l] : 0;
+  return B ? B->ranks.d_rank[l] : nullptr;
 }
 
 hipError_t dev_batch_reserve(perc_ctx* h, int list, int ntrials, int** d_rank) {
-  BatchState* B = batch_state(h);
-  const bool bonds = list == PERC_BOND;
-  int** p = bonds ? &B->d_rank : &B->d_rank_s;
-  size_t* cap = bonds ? &B->rank_cap : &B->rank_s_cap;
-  int* have = bonds ? &B->ntrials : &B->ntrials_s;
-  const size_t n = (size_t)ntrials * (size_t)(bonds ? h->nb : h->g.t);
-  *have = 0;
-  HIP_TRY(grow(p, cap, n));
-  *have = ntrials;
-  *d_rank = *p;
+  RankStore& R = batch_state(h)->ranks;
+  const int l = rank_slot(list);
+  R.held[l] = 0;
+  HIP_TRY(grow(&R.d_rank[l], &R.cap[l], (size_t)ntrials * rank_len(h, list)));
+  R.held[l] = ntrials;
+  *d_rank = R.d_rank[l];
   return hipSuccess;
 }
 
-hipError_t dev_batch_upload(perc_ctx* h, int ntrials, const int* rank) {
-  BatchState* B = batch_state(h);
-  B->ntrials = 0;
-  HIP_TRY(upload_ranks(&B->d_rank, &B->rank_cap, (size_t)ntrials * (size_t)h->nb, rank, h->stream));
-  B->ntrials = ntrials;
+hipError_t dev_batch_stage(perc_ctx* h, int list, int ntrials, int** row) {
+  RankStore& R = batch_state(h)->ranks;
+  const int l = rank_slot(list);
+  if (R.in_flight[l]) HIP_TRY(hipStreamSynchronize(h->stream));
+  R.in_flight[l] = false;
+  HIP_TRY(grow_pinned(&R.h_row[l], &R.hcap[l], (size_t)ntrials * rank_len(h, list)));
+  *row = R.h_row[l];
   return hipSuccess;
 }
 
-hipError_t dev_batch_upload_sites(perc_ctx* h, int ntrials, const int* rank_s) {
-  BatchState* B = batch_state(h);
-  B->ntrials_s = 0;
-  HIP_TRY(upload_ranks(&B->d_rank_s, &B->rank_s_cap, (size_t)ntrials * (size_t)h->g.t, rank_s, h->stream));
-  B->ntrials_s = ntrials;
+hipError_t dev_batch_commit(perc_ctx* h, int list, int ntrials) {
+  RankStore& R = batch_state(h)->ranks;
+  const int l = rank_slot(list);
+  const size_t n = (size_t)ntrials * rank_len(h, list);
+  if (R.hcap[l] < n) return hipErrorInvalidValue;  // (no stage of that many trials)
+  int* d_rank = nullptr;
+  HIP_TRY(dev_batch_reserve(h, list, ntrials, &d_rank));
+  R.in_flight[l] = n > 0;
+  if (n) HIP_TRY(hipMemcpyAsync(d_rank, R.h_row[l], sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
   return hipSuccess;
 }
 
@@ -398,20 +401,20 @@ hipError_t dev_batch_twister(perc_ctx* h, int nseeds, const unsigned* seeds, lon
   return hipSuccess;
 }
 
-hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const int* item_trial,
-                         const int* item_nsites, const int* item_count, int solve, double Va,
-                         double g0, double leak, int itol, double tol, int itmax, bool literal,
-                         BatchOut* out, double* iout, bool large, const BatchWeights* wts,
-                         const BatchFields* fld) {
+hipError_t dev_batch_run(perc_ctx* h, int kind, const BatchSolve& sv, int nitems, const int* item_trial,
+                         const int* item_nsites, const int* item_count, BatchOut* out, double* iout, bool large,
+                         const BatchWeights* wts, const BatchFields* fld) {
   if (nitems == 0) return hipSuccess;
   BatchState* B = batch_state(h);
   hipStream_t st = h->stream;
   const int m = h->g.m;
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
-  // every item's trial must lie in the uploaded rank arrays the kind reads
-  int have = INT_MAX;
-  if (need_b) have = std::min(have, B->d_rank ? B->ntrials : 0);
-  if (need_s) have = std::min(have, B->d_rank_s ? B->ntrials_s : 0);
+  // every item's trial must lie in the rank arrays the store holds for the kind
+  int have = INT_MAX, held = 0;
+  const int* d_rank_b = dev_batch_ranks(h, PERC_BOND, &held);
+  if (need_b) have = std::min(have, held);
+  const int* d_rank_s = dev_batch_ranks(h, PERC_SITE, &held);
+  if (need_s) have = std::min(have, held);
   for (int i = 0; i < nitems; ++i)
     if (item_trial[i] < 0 || item_trial[i] >= have) {
       set_error("k_batch_cond: an item's trial lies outside the uploaded rank arrays");
@@ -421,21 +424,12 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
     HIP_TRY(dmalloc(&B->d_sflag, 4));
     HIP_TRY(hipMemsetAsync(B->d_sflag, 0, 4 * sizeof(int), st));
   }
-  if (B->item_cap < (size_t)nitems) {  // d_items and d_out share one capacity
-    size_t c3 = 0, c1 = 0;  // zero on purpose: grow() frees and allocates both afresh
-    B->item_cap = 0;
-    HIP_TRY(grow(&B->d_items, &c3, 3 * (size_t)nitems));
-    HIP_TRY(grow(&B->d_out, &c1, (size_t)nitems));
-    B->item_cap = nitems;
-  }
+  const int solve = sv.solve ? 1 : 0;
+  const bool literal = sv.literal;
   const size_t niout = solve ? (size_t)nitems * 2 * m : 0;
   HIP_TRY(grow(&B->d_iout, &B->iout_cap, niout));
-  HIP_TRY(hipMemcpyAsync(B->d_items, item_trial, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
-  if (need_b)
-    HIP_TRY(hipMemcpyAsync(B->d_items + nitems, item_count, sizeof(int) * nitems, hipMemcpyHostToDevice, st));
-  if (need_s)
-    HIP_TRY(hipMemcpyAsync(B->d_items + 2 * (size_t)nitems, item_nsites, sizeof(int) * nitems,
-                           hipMemcpyHostToDevice, st));
+  HIP_TRY(B->items.upload((size_t)nitems,
+                          {item_trial, need_b ? item_count : nullptr, need_s ? item_nsites : nullptr}, st));
   // an item that stops before the currents leaves its iout row unwritten
   if (niout) HIP_TRY(hipMemsetAsync(B->d_iout, 0, sizeof(double) * niout, st));
   // ... and its record and voltages: all zero
@@ -452,24 +446,24 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
   c.nb = (int)h->nb;
   c.bond_first = h->d.bond_first;
   c.forms = h->d.forms_dev;
-  c.rank = B->d_rank;
-  c.rank_s = B->d_rank_s;
-  c.item_trial = B->d_items;
-  c.item_count = B->d_items + nitems;
-  c.item_nsites = B->d_items + 2 * (size_t)nitems;
-  c.out = B->d_out;
+  c.rank = d_rank_b;
+  c.rank_s = d_rank_s;
+  c.item_trial = B->items.list(0, nitems);
+  c.item_count = B->items.list(1, nitems);
+  c.item_nsites = B->items.list(2, nitems);
+  c.out = B->items.d_out;
   c.iout = B->d_iout;
   c.sflag = B->d_sflag;
   asm_closed_forms(h, &c.fast, &c.fl, &c.fr);
   c.bf_closed = h->bf_closed ? 1 : 0;
   c.solve = solve;
-  c.itol = itol;
-  c.itmax = itmax;
-  c.cur_rule = cur_rule;
-  c.Va = Va;
-  c.g0 = g0;
-  c.leak = leak;
-  c.tol = tol;
+  c.itol = sv.itol;
+  c.itmax = sv.itmax;
+  c.cur_rule = sv.cur_rule;
+  c.Va = sv.Va;
+  c.g0 = sv.g0;
+  c.leak = sv.leak;
+  c.tol = sv.tol;
   hipError_t e;
   if (fld) {  // k_batch_cond's FIELDS instantiations: the common block, the plan and the fields
     BatchFieldArgs a;
@@ -530,7 +524,7 @@ hipError_t dev_batch_run(perc_ctx* h, int kind, int cur_rule, int nitems, const 
   }
   HIP_TRY(e);
   int flag = 0;
-  HIP_TRY(hipMemcpyAsync(out, B->d_out, sizeof(BatchOut) * nitems, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out, B->items.d_out, sizeof(BatchOut) * nitems, hipMemcpyDeviceToHost, st));
   if (niout) HIP_TRY(hipMemcpyAsync(iout, B->d_iout, sizeof(double) * niout, hipMemcpyDeviceToHost, st));
   if (fld) {
     HIP_TRY(hipMemcpyAsync(fld->cur, B->d_cur, sizeof(perc_batch_currents) * nitems, hipMemcpyDeviceToHost, st));

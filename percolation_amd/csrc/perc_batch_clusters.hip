@@ -160,18 +160,7 @@ __global__ __launch_bounds__(NT) void k_batch_clusters(ClusterArgs a) {
 }
 
 struct ClusterState {
-  int* d_rank_s = nullptr;
-  int* d_rank_b = nullptr;
-  size_t cap_s = 0, cap_b = 0;
-  // pinned host rows the call forms its ranks in (dev_clusters_stage): a
-  // fresh pageable array of a launch's 64 MB costs more in page faults and the
-  // runtime's staged copy than the kernel runs
-  int* h_rank_s = nullptr;
-  int* h_rank_b = nullptr;
-  size_t hcap_s = 0, hcap_b = 0;
-  int* d_items = nullptr;  // item_trial, then item_nsites, then item_nbonds
-  perc_cluster_item* d_out = nullptr;
-  size_t item_cap = 0;
+  ItemLists<perc_cluster_item, 3> items;  // item_trial, then item_nsites, then item_nbonds
   int* d_hist = nullptr;
   size_t hist_cap = 0;
   int lds_attr[3][3] = {};  // dynamic LDS granted per instantiation
@@ -182,37 +171,12 @@ ClusterState* cluster_state(perc_ctx* h) {
   return static_cast<ClusterState*>(h->clusters);
 }
 
-// *p (pinned host, capacity *cap) grown to n ints; the contents are not kept
-hipError_t grow_pinned(int** p, size_t* cap, size_t n) {
-  if (*cap >= n) return hipSuccess;
-  if (*p) HIP_TRY(hipHostFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(p), sizeof(int) * n, hipHostMallocDefault));
-  *cap = n;
-  return hipSuccess;
-}
-
 }  // namespace
-
-hipError_t dev_clusters_stage(perc_ctx* h, size_t ns, size_t nbk, int** rank_s, int** rank_b) {
-  ClusterState* S = cluster_state(h);
-  HIP_TRY(grow_pinned(&S->h_rank_s, &S->hcap_s, ns));
-  HIP_TRY(grow_pinned(&S->h_rank_b, &S->hcap_b, nbk));
-  *rank_s = S->h_rank_s;
-  *rank_b = S->h_rank_b;
-  return hipSuccess;
-}
 
 void dev_clusters_free(perc_ctx* h) {
   ClusterState* S = static_cast<ClusterState*>(h->clusters);
   if (!S) return;
-  (void)hipFree(S->d_rank_s);
-  (void)hipFree(S->d_rank_b);
-  if (S->h_rank_s) (void)hipHostFree(S->h_rank_s);
-  if (S->h_rank_b) (void)hipHostFree(S->h_rank_b);
-  (void)hipFree(S->d_items);
-  (void)hipFree(S->d_out);
+  S->items.release();
   (void)hipFree(S->d_hist);
   delete S;
   h->clusters = nullptr;
@@ -225,19 +189,9 @@ hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank
   ClusterState* S = cluster_state(h);
   hipStream_t st = h->stream;
   const size_t n = (size_t)nitems, nh = (size_t)nexact + 32;
-  if (S->item_cap < n) {  // d_items and d_out share one capacity
-    size_t ci = 0, co = 0;  // zero on purpose: grow() frees and allocates both afresh
-    S->item_cap = 0;
-    HIP_TRY(grow(&S->d_items, &ci, 3 * n));
-    HIP_TRY(grow(&S->d_out, &co, n));
-    S->item_cap = n;
-  }
   if (hist) HIP_TRY(grow(&S->d_hist, &S->hist_cap, n * nh));
-  HIP_TRY(hipMemcpyAsync(S->d_items, item_trial, sizeof(int) * n, hipMemcpyHostToDevice, st));
-  if (kind != PERC_BOND)
-    HIP_TRY(hipMemcpyAsync(S->d_items + n, item_nsites, sizeof(int) * n, hipMemcpyHostToDevice, st));
-  if (kind != PERC_SITE)
-    HIP_TRY(hipMemcpyAsync(S->d_items + 2 * n, item_nbonds, sizeof(int) * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(S->items.upload(n, {item_trial, kind != PERC_BOND ? item_nsites : nullptr,
+                              kind != PERC_SITE ? item_nbonds : nullptr}, st));
   ClusterArgs a;
   a.g = h->g;
   a.nb = (int)h->nb;
@@ -245,10 +199,10 @@ hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank
   a.bond_first = h->d.bond_first;
   a.rank_s = d_rank_s;
   a.rank_b = d_rank_b;
-  a.item_trial = S->d_items;
-  a.item_nsites = S->d_items + n;
-  a.item_nbonds = S->d_items + 2 * n;
-  a.out = S->d_out;
+  a.item_trial = S->items.list(0, n);
+  a.item_nsites = S->items.list(1, n);
+  a.item_nbonds = S->items.list(2, n);
+  a.out = S->items.d_out;
   a.hist = hist ? S->d_hist : nullptr;
   a.L = cluster_lds(h->g, nexact);
   HIP_TRY(dispatch_threads(scan_threads(h->g.t), [&](auto nt, int slot) {
@@ -257,25 +211,9 @@ hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank
                         "k_batch_clusters");
     });
   }));
-  HIP_TRY(hipMemcpyAsync(out, S->d_out, sizeof(perc_cluster_item) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out, S->items.d_out, sizeof(perc_cluster_item) * n, hipMemcpyDeviceToHost, st));
   if (hist) HIP_TRY(hipMemcpyAsync(hist, S->d_hist, sizeof(int) * n * nh, hipMemcpyDeviceToHost, st));
   return hipStreamSynchronize(st);  // (the item lists and the outputs are the caller's)
-}
-
-hipError_t dev_clusters_upload_run(perc_ctx* h, int kind, int ntrials, const int* rank_s, const int* rank_b,
-                                   int nitems, const int* item_trial, const int* item_nsites,
-                                   const int* item_nbonds, int nexact, perc_cluster_item* out, int* hist) {
-  if (nitems == 0) return hipSuccess;
-  ClusterState* S = cluster_state(h);
-  hipStream_t st = h->stream;
-  const size_t ns = rank_s ? (size_t)ntrials * (size_t)h->g.t : 0;
-  const size_t nbk = rank_b ? (size_t)ntrials * (size_t)h->nb : 0;
-  HIP_TRY(grow(&S->d_rank_s, &S->cap_s, ns));
-  HIP_TRY(grow(&S->d_rank_b, &S->cap_b, nbk));
-  if (ns) HIP_TRY(hipMemcpyAsync(S->d_rank_s, rank_s, sizeof(int) * ns, hipMemcpyHostToDevice, st));
-  if (nbk) HIP_TRY(hipMemcpyAsync(S->d_rank_b, rank_b, sizeof(int) * nbk, hipMemcpyHostToDevice, st));
-  return dev_clusters_run(h, kind, nitems, ns ? S->d_rank_s : nullptr, nbk ? S->d_rank_b : nullptr,
-                          item_trial, item_nsites, item_nbonds, nexact, out, hist);
 }
 
 }  // namespace perc

@@ -8,8 +8,14 @@
 // perc_batch_clusters, perc_batch_clusters_seeded, and the current
 // distributions' perc_batch_currents_supported, perc_batch_cond_currents,
 // perc_batch_cond_currents_seeded, perc_current_stats_host):
-// argument checks, the orders' inverse permutations, the
-// launch geometry and LDS layouts, the fold of the terminal currents and the
+// the launch geometry and LDS layouts, then the calls.  Who owns what: every
+// entry point keeps the checks of its own path (rule pairing, cut, nexact,
+// fixed, its *_supported and that message) and shares perc_batch_plan.h's
+// check_items and ItemRuns and, per run, provide_ranks -- the one place that
+// turns order lists or seed lists into rank arrays in the context's rank
+// store (perc_batch.h).  batch_cond_impl is the front door of every
+// conductance call, perc_batch_bondc included; batch_run_items_kind its run
+// loop: one launch per run, the fold of the terminal currents and the
 // single-path replay of the items several clusters span.
 #include <hip/hip_runtime.h>
 
@@ -22,6 +28,7 @@
 #include <vector>
 
 #include "perc_batch.h"
+#include "perc_batch_plan.h"
 
 namespace perc {
 
@@ -213,76 +220,78 @@ bool shuffle_supported(int N) {
   return shuffle_lds(N).total <= kBatchLdsMax;
 }
 
-// rank[tr * N + id - 1] = position of id in trial tr's order of N + 1 entries
-// (the spill slot 0 takes a position and is no element; INT_MAX: absent)
-static void order_ranks(int ntrials, int N, const int* orders, int* rank) {
-  std::fill(rank, rank + (size_t)ntrials * N, INT_MAX);
-  for (int tr = 0; tr < ntrials; ++tr) {
-    const int* o = orders + (size_t)tr * (N + 1);
-    int* r = rank + (size_t)tr * N;
-    for (int pos = 0; pos <= N; ++pos) {
-      const int id = o[pos];
-      if (id >= 1 && id <= N && r[id - 1] == INT_MAX) r[id - 1] = pos;
-    }
+// One list's ranks of a run into the rank store: the run's trial j is the
+// call's trial used[j] (used NULL: first + j).  Orders: their inverse
+// permutations formed in the store's pinned row, then committed; seeds: the
+// device shuffle, which fills the store itself.
+static hipError_t provide_list(perc_ctx* h, int list, const BatchSources& src, int first, const int* used, int k,
+                               std::vector<int>* seeds) {
+  const int N = list == PERC_BOND ? (int)h->nb : h->g.t;
+  const int* from = list == PERC_BOND ? src.bond_src : src.site_src;
+  auto trial = [&](int j) { return (size_t)(used ? used[j] : first + j); };
+  if (src.seeded) {
+    seeds->resize((size_t)k);
+    for (int j = 0; j < k; ++j) (*seeds)[j] = from[trial(j)];
+    return dev_shuffle_run(h, list, k, seeds->data(), nullptr, nullptr);
   }
+  int* row = nullptr;
+  const hipError_t e = dev_batch_stage(h, list, k, &row);
+  if (e != hipSuccess) return e;
+  for (int j = 0; j < k; ++j) order_ranks(1, N, from + trial(j) * (N + 1), row + (size_t)j * N);
+  return dev_batch_commit(h, list, k);
+}
+
+// ... of the lists the kind reads: the one orders-or-seeds switch of the
+// conductance, scan and cluster calls.  d_s / d_b (optional): the store's
+// ranks of the lists the kind reads, for a launch that takes them as pointers
+static hipError_t provide_ranks(perc_ctx* h, int kind, const BatchSources& src, int first, const int* used,
+                                int k, const int** d_s = nullptr, const int** d_b = nullptr) {
+  std::vector<int> seeds;
+  hipError_t e = hipSuccess;
+  int held = 0;
+  if (kind != PERC_BOND) e = provide_list(h, PERC_SITE, src, first, used, k, &seeds);
+  if (e == hipSuccess && kind != PERC_SITE) e = provide_list(h, PERC_BOND, src, first, used, k, &seeds);
+  if (d_s) *d_s = kind != PERC_BOND ? dev_batch_ranks(h, PERC_SITE, &held) : nullptr;
+  if (d_b) *d_b = kind != PERC_SITE ? dev_batch_ranks(h, PERC_BOND, &held) : nullptr;
+  return e;
+}
+
+// the most trials of the lists the kind reads whose rank arrays stay under
+// 64 MB of device memory per run
+static long long rank_run_cap(perc_ctx* h, int kind) {
+  return (64LL << 20) / (4LL * ((kind != PERC_BOND ? h->g.t : 0) + (kind != PERC_SITE ? h->nb : 0)));
 }
 
 int batch_upload_orders(perc_ctx* h, int ntrials, const int* orders) {
-  const int nb = (int)h->nb;
   hipSetDevice(h->device);
-  std::vector<int> rank((size_t)ntrials * nb);
-  order_ranks(ntrials, nb, orders, rank.data());
-  hipError_t e = dev_batch_upload(h, ntrials, rank.data());
-  if (e != hipSuccess) return hip_status(e, "perc_batch_bondc/upload");
-  return PERC_OK;
+  BatchSources src;
+  src.bond_src = orders;
+  return hip_status(provide_ranks(h, PERC_BOND, src, 0, nullptr, ntrials), "perc_batch_bondc/upload");
 }
 
-int batch_upload_site_orders(perc_ctx* h, int ntrials, const int* site_orders) {
-  const int t = h->g.t;
-  hipSetDevice(h->device);
-  std::vector<int> rank((size_t)ntrials * t);
-  order_ranks(ntrials, t, site_orders, rank.data());
-  hipError_t e = dev_batch_upload_sites(h, ntrials, rank.data());
-  if (e != hipSuccess) return hip_status(e, "perc_batch_cond/upload");
-  return PERC_OK;
-}
-
-// the first cnt entries of an order of N + 1 as perc_occupy takes them: the
-// whole order (cnt > N) with the spill slot dropped
-static bool occupy_prefix(const int* o, int cnt, int N, std::vector<int>* list, const int** src,
-                          int* len) {
-  *src = o;
-  *len = cnt;
-  if (cnt <= N) return true;
-  list->clear();
-  for (int k = 0; k < cnt; ++k)
-    if (o[k] != 0) list->push_back(o[k]);
-  if ((int)list->size() > N) return false;
-  *src = list->data();
-  *len = (int)list->size();
-  return true;
-}
-
-int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_orders,
-                         const int* bond_orders, int nitems, const int* item_trial,
-                         const int* item_nsites, const int* item_nbonds, int solve, bool replay,
-                         double Va, double g0, double leak, int itol, double tol, int itmax,
-                         perc_batch_item* out, const int* site_seeds, const int* bond_seeds,
-                         const BatchWeights* wts, const BatchFields* fld) {
+int batch_run_items_kind(perc_ctx* h, int kind, int ntrials, const BatchSources& src, int nitems,
+                         const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                         const BatchSolve& sv_in, perc_batch_item* out, const BatchWeights* wts,
+                         const BatchFields* fld) {
   const int nb = (int)h->nb, m = h->g.m, t = h->g.t;
   const size_t N = (size_t)h->N;
   const int rule = kind;  // (PERC_RULE_* of a kind has the kind's number)
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
+  BatchSolve sv = sv_in;
+  sv.literal = h->dot_order != PERC_DOT_FAST;
+  const int solve = sv.solve, cur_rule = sv.cur_rule;
+  const double Va = sv.Va;
   const char* who = kind == PERC_BOND && cur_rule == PERC_CUR_FORTRAN ? "perc_batch_bondc" : "perc_batch_cond";
   hipSetDevice(h->device);
   hipError_t e;
-  const bool literal = h->dot_order != PERC_DOT_FAST;
   // launches of bounded size (the iout rows: 16 m bytes per item)
   int chunk = std::max(1, std::min(16384, (int)((64LL << 20) / (16LL * m))));
   // ... and the weighted kernel's rows (its draws, its scratch: 8 nb bytes per item each)
   if (wts) chunk = std::max(1, std::min(chunk, (int)((64LL << 20) / (8LL * (nb + 16)))));
   // ... and the interior voltages (8 N bytes per item)
   if (fld && fld->vint) chunk = std::max(1, std::min(chunk, (int)((64LL << 20) / (16LL * m + 8LL * (long long)N))));
+  // ... and the rank arrays of the trials a run names (at most one per item)
+  if (!src.held) chunk = (int)std::max(1LL, std::min<long long>(chunk, rank_run_cap(h, kind)));
   std::vector<BatchOut> bo((size_t)std::min(nitems, chunk));
   // a fallback item's record on the host: the bond list, the mask, the voltages
   std::vector<int> fb1, fb2, canon;
@@ -290,8 +299,13 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
   std::vector<double> fvint;
   std::vector<double> iout(solve ? bo.size() * 2 * (size_t)m : 0);
   std::vector<int> slist, blist, sregen, bregen;
-  for (int i0 = 0; i0 < nitems; i0 += chunk) {
-    const int n = std::min(chunk, nitems - i0);
+  ItemRuns runs(src.held ? nullptr : item_trial, nitems, ntrials, chunk);
+  while (runs.next()) {
+    const int i0 = runs.i0, n = runs.n;
+    if (!src.held) {
+      e = provide_ranks(h, kind, src, 0, runs.used.data(), (int)runs.used.size());
+      if (e != hipSuccess) return hip_status(e, who);
+    }
     BatchWeights wc;
     if (wts) {
       wc = *wts;
@@ -304,10 +318,9 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
       fc.cur += i0;
       if (fc.vint) fc.vint += (size_t)i0 * N;
     }
-    e = dev_batch_run(h, kind, cur_rule, n, item_trial + i0, need_s ? item_nsites + i0 : nullptr,
-                      need_b ? item_nbonds + i0 : nullptr, solve ? 1 : 0, Va, g0, leak, itol, tol, itmax,
-                      literal, bo.data(), iout.data(), wts || fld ? false : h->batch_large, wts ? &wc : nullptr,
-                      fld ? &fc : nullptr);
+    e = dev_batch_run(h, kind, sv, n, src.held ? item_trial + i0 : runs.local.data(),
+                      need_s ? item_nsites + i0 : nullptr, need_b ? item_nbonds + i0 : nullptr, bo.data(),
+                      iout.data(), wts || fld ? false : h->batch_large, wts ? &wc : nullptr, fld ? &fc : nullptr);
     if (e != hipSuccess) return hip_status(e, who);
     for (int i = 0; i < n; ++i) {
       perc_batch_item& it = out[i0 + i];
@@ -321,26 +334,22 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
       it.status = b.status;
       it.iter = b.iter;
       it.err = b.err;
-      if (b.fallback && replay) {
+      if (b.fallback && src.replay) {
         // several clusters span: the reference's lowest-label rule through
         // the single path, on the context
         const int tr = item_trial[i0 + i];
         const int *ssrc = nullptr, *bsrc = nullptr;
         int slen = 0, blen = 0;
-        const int* so = need_s && site_orders ? site_orders + (size_t)tr * (t + 1) : nullptr;
-        const int* bo = need_b && bond_orders ? bond_orders + (size_t)tr * (nb + 1) : nullptr;
-        if (need_s && !so) {  // the seeded call: this trial's order, on the host
-          if (!site_seeds) return PERC_EINVAL;
-          sregen.resize((size_t)t + 1);
-          perc_shuffle_seeded(site_seeds[tr], t, sregen.data());
-          so = sregen.data();
-        }
-        if (need_b && !bo) {
-          if (!bond_seeds) return PERC_EINVAL;
-          bregen.resize((size_t)nb + 1);
-          perc_shuffle_seeded(bond_seeds[tr], nb, bregen.data());
-          bo = bregen.data();
-        }
+        if ((need_s && !src.site_src) || (need_b && !src.bond_src)) return PERC_EINVAL;
+        // the caller's trial's order of a list; seeded: regenerated on the host
+        auto order_of = [&](const int* from, int len, std::vector<int>* regen) {
+          if (!src.seeded) return from + (size_t)tr * (len + 1);
+          regen->resize((size_t)len + 1);
+          perc_shuffle_seeded(from[tr], len, regen->data());
+          return (const int*)regen->data();
+        };
+        const int* so = need_s ? order_of(src.site_src, t, &sregen) : nullptr;
+        const int* bo = need_b ? order_of(src.bond_src, nb, &bregen) : nullptr;
         if (need_s && !occupy_prefix(so, item_nsites[i0 + i], t, &slist, &ssrc, &slen)) return PERC_EINVAL;
         if (need_b && !occupy_prefix(bo, item_nbonds[i0 + i], nb, &blist, &bsrc, &blen)) return PERC_EINVAL;
         perc_label_info li{};
@@ -365,7 +374,7 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
             fvint.resize(N);
             vrow = fld->vint ? fc.vint + (size_t)i * N : fvint.data();
           }
-          if (!rc) rc = perc_conductance(h, rule, cur_rule, Va, g0, leak, itol, tol, itmax, &res, vrow);
+          if (!rc) rc = perc_conductance(h, rule, cur_rule, Va, sv.g0, sv.leak, sv.itol, sv.tol, sv.itmax, &res, vrow);
           if (!rc && fld && res.status == 0) {
             // the conducting mask from the occupancy lists and the canonical
             // labels (bond_value's three rules: a conducting bond's end sites
@@ -387,7 +396,7 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
               const bool occ = (!need_b || focc_b[id]) && (!need_s || (focc_s[s1] && focc_s[s2]));
               fmask[id - 1] = occ && li.span_root > 0 && canon[s1 - 1] == li.span_root;
             }
-            rc = perc_current_stats_host(h->g.lattice, m, h->g.n, h->g.pbc, fmask.data(), vrow, Va, g0, fld->cut,
+            rc = perc_current_stats_host(h->g.lattice, m, h->g.n, h->g.pbc, fmask.data(), vrow, Va, sv.g0, fld->cut,
                                          &fc.cur[i]);
           } else if (!rc && fld && fld->vint) {
             std::fill(vrow, vrow + N, 0.0);
@@ -430,14 +439,18 @@ int batch_run_items_kind(perc_ctx* h, int kind, int cur_rule, const int* site_or
 int batch_run_items(perc_ctx* h, const int* orders, int nitems, const int* item_trial,
                     const int* item_count, int solve, bool replay, double Va, double g0, double leak,
                     int itol, double tol, int itmax, perc_batch_item* out) {
-  return batch_run_items_kind(h, PERC_BOND, PERC_CUR_FORTRAN, nullptr, orders, nitems, item_trial, nullptr,
-                              item_count, solve, replay, Va, g0, leak, itol, tol, itmax, out);
+  BatchSources src;
+  src.bond_src = orders;
+  src.held = true;
+  src.replay = replay;
+  return batch_run_items_kind(h, PERC_BOND, 0, src, nitems, item_trial, nullptr, item_count,
+                              BatchSolve{solve, PERC_CUR_FORTRAN, Va, g0, leak, itol, tol, itmax}, out);
 }
 
 int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out) {
   hipSetDevice(h->device);
   int have = 0;
-  const int* d_rank = dev_batch_ranks(h, &have);
+  const int* d_rank = dev_batch_ranks(h, PERC_BOND, &have);
   if (!d_rank || have < ntrials) {
     set_error("batch_scan_uploaded: no uploaded group of that many trials");
     return PERC_ESTATE;
@@ -445,6 +458,12 @@ int batch_scan_uploaded(perc_ctx* h, int ntrials, perc_scan_item* out) {
   return hip_status(dev_scan_run(h, PERC_BOND, PERC_BOND, ntrials, nullptr, d_rank, nullptr, out),
                     "perc_batch_scan");
 }
+
+// the lists the kind reads within the device shuffle's reach
+static bool shuffle_lists_ok(perc_ctx* h, int kind) {
+  return (kind == PERC_BOND || shuffle_supported(h->g.t)) && (kind == PERC_SITE || shuffle_supported((int)h->nb));
+}
+static const char* const kShuffleReach = "a list too long for the device shuffle (perc_shuffle_device_supported)";
 
 }  // namespace perc
 
@@ -456,39 +475,6 @@ int perc_batch_supported(int lattice, int m, int n, int pbc) {
   if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
   if (m < 1 || n < 1 || (long long)m * n >= (1LL << 31) - 16) return 0;
   return batch_supported(make_geom(lattice, m, n, pbc)) ? 1 : 0;
-}
-
-int perc_batch_bondc(perc_ctx* h, int ntrials, const int* orders, int nitems, const int* item_trial,
-                     const int* item_count, int solve, double Va, double g0, double leak, int itol,
-                     double tol, int itmax, perc_batch_item* out) {
-  if (!h || ntrials < 0 || nitems < 0 || (ntrials && !orders) ||
-      (nitems && (!item_trial || !item_count || !out)) || itmax < 0)
-    return PERC_EINVAL;
-  if (solve && itol != 1 && itol != 2) {
-    set_error("perc_batch_bondc: itol 1 or 2 only");
-    return PERC_EINVAL;
-  }
-  if (h->batch_large) {
-    if (!batch_large_supported(h->g, PERC_BOND)) {
-      set_error("perc_batch_bondc: lattice not supported by the large batch kernel "
-                "(perc_batch_large_supported)");
-      return PERC_EINVAL;
-    }
-  } else if (!batch_supported(h->g)) {
-    set_error("perc_batch_bondc: lattice not supported by the batch kernel (perc_batch_supported)");
-    return PERC_EINVAL;
-  }
-  const int nb = (int)h->nb;
-  for (int i = 0; i < nitems; ++i)
-    if (item_trial[i] < 0 || item_trial[i] >= ntrials || item_count[i] < 0 || item_count[i] > nb + 1) {
-      set_error("perc_batch_bondc: item_trial outside 0..ntrials-1 or item_count outside 0..nb+1");
-      return PERC_EINVAL;
-    }
-  if (nitems == 0) return PERC_OK;
-  int rc = batch_upload_orders(h, ntrials, orders);
-  if (rc) return rc;
-  return batch_run_items(h, orders, nitems, item_trial, item_count, solve, true, Va, g0, leak, itol,
-                         tol, itmax, out);
 }
 
 int perc_batch_cond_supported(int kind, int lattice, int m, int n, int pbc) {
@@ -513,18 +499,23 @@ int perc_set_batch_large(perc_ctx* h, int enable) {
 
 int perc_batch_large(perc_ctx* h) { return h ? (h->batch_large ? 1 : 0) : PERC_EINVAL; }
 
-// perc_batch_cond (seeded = false: site_src / bond_src are order lists) and
-// perc_batch_cond_seeded (true: seed lists, the orders shuffled on the device)
-static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, int rule, int cur_rule,
-                           int ntrials, const int* site_src, const int* bond_src, int nitems,
-                           const int* item_trial, const int* item_nsites, const int* item_nbonds,
-                           int solve, double Va, double g0, double leak, int itol, double tol, int itmax,
+// The one front door of the conductance calls: perc_batch_cond and its
+// weighted and currents forms (seeded = false: site_src / bond_src are order
+// lists), the seeded forms (true: seed lists, the orders shuffled on the
+// device) and perc_batch_bondc (bondc: its own predicates' names in the texts)
+static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, int rule, int ntrials,
+                           const int* site_src, const int* bond_src, int nitems, const int* item_trial,
+                           const int* item_nsites, const int* item_nbonds, const BatchSolve& sv,
                            perc_batch_item* out, const BatchWeights* wts = nullptr,
-                           const BatchFields* fld = nullptr) {
+                           const BatchFields* fld = nullptr, bool bondc = false) {
   if (!h) return PERC_EINVAL;
-  auto bad = [who](const char* text) {
+  auto bad = [who](const std::string& text) {
     set_error(std::string(who) + ": " + text);
     return PERC_EINVAL;
+  };
+  auto unsupported = [&](const char* kernel, const char* predicate) {
+    return bad(std::string("lattice not supported by the ") + kernel + (bondc ? " (" : " for this kind (") +
+               predicate + ")");
   };
   const bool pair = (kind == PERC_BOND && rule == PERC_RULE_BOND) ||
                     (kind == PERC_SITE && rule == PERC_RULE_SITE) ||
@@ -532,70 +523,55 @@ static int batch_cond_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
   if (!pair)
     return bad("kind / rule PERC_BOND / PERC_RULE_BOND, PERC_SITE / PERC_RULE_SITE or PERC_SITEBOND / "
                "PERC_RULE_MIXED only");
-  if (cur_rule != PERC_CUR_FORTRAN && cur_rule != PERC_CUR_MATLAB)
+  if (sv.cur_rule != PERC_CUR_FORTRAN && sv.cur_rule != PERC_CUR_MATLAB)
     return bad("cur_rule PERC_CUR_FORTRAN or PERC_CUR_MATLAB only");
   if (ntrials < 0 || nitems < 0) return bad("ntrials or nitems < 0");
-  if (itmax < 0) return bad("itmax < 0");
-  if (solve && itol != 1 && itol != 2) return bad("itol 1 or 2 only");
+  if (sv.itmax < 0) return bad("itmax < 0");
+  if (sv.solve && sv.itol != 1 && sv.itol != 2) return bad("itol 1 or 2 only");
   if (fld) {  // the default kernel only: the perc_set_batch_large flag is not read
     if (nitems && !fld->cur) return bad("cur missing");
     if (!(fld->cut >= 0.0 && fld->cut <= 1.0)) return bad("cut outside [0, 1]");
-    if (!batch_supported(h->g, kind))
-      return bad("lattice not supported by the batch kernel for this kind (perc_batch_currents_supported)");
+    if (!batch_supported(h->g, kind)) return unsupported("batch kernel", "perc_batch_currents_supported");
   } else if (wts) {  // its own kernel: the perc_set_batch_large flag is not read
     if (!batch_w_supported(h->g, kind))
-      return bad("lattice not supported by the weighted batch kernel for this kind "
-                 "(perc_batch_weighted_supported)");
+      return unsupported("weighted batch kernel", "perc_batch_weighted_supported");
   } else if (h->batch_large) {
-    if (!batch_large_supported(h->g, kind))
-      return bad("lattice not supported by the large batch kernel for this kind "
-                 "(perc_batch_large_supported)");
+    if (!batch_large_supported(h->g, kind)) return unsupported("large batch kernel", "perc_batch_large_supported");
   } else if (!batch_supported(h->g, kind)) {
-    return bad("lattice not supported by the batch kernel for this kind (perc_batch_cond_supported)");
+    return unsupported("batch kernel", bondc ? "perc_batch_supported" : "perc_batch_cond_supported");
   }
-  const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
-  if (ntrials && ((need_s && !site_src) || (need_b && !bond_src)))
-    return bad(seeded ? "a seed list the kind reads is missing" : "an order list the kind reads is missing");
-  if (nitems && (!item_trial || !out || (need_s && !item_nsites) || (need_b && !item_nbonds)))
-    return bad("item_trial, out or a count list the kind reads is missing");
-  const int t = h->g.t, nb = (int)h->nb;
-  for (int i = 0; i < nitems; ++i) {
-    if (item_trial[i] < 0 || item_trial[i] >= ntrials) return bad("item_trial outside 0..ntrials-1");
-    if (need_s && (item_nsites[i] < 0 || item_nsites[i] > t + 1)) return bad("item_nsites outside 0..t+1");
-    if (need_b && (item_nbonds[i] < 0 || item_nbonds[i] > nb + 1)) return bad("item_nbonds outside 0..nb+1");
-  }
-  if (seeded && ((need_s && !shuffle_supported(t)) || (need_b && !shuffle_supported(nb))))
-    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (const char* text = check_items(kind != PERC_BOND, kind != PERC_SITE, seeded, ntrials, site_src, bond_src,
+                                     nitems, item_trial, item_nsites, item_nbonds, out, h->g.t, (int)h->nb))
+    return bad(text);
+  if (seeded && !shuffle_lists_ok(h, kind)) return bad(kShuffleReach);
   if (nitems == 0) return PERC_OK;
-  if (seeded) {
-    hipSetDevice(h->device);
-    if (need_b) {
-      const hipError_t e = dev_shuffle_run(h, PERC_BOND, ntrials, bond_src, nullptr, nullptr);
-      if (e != hipSuccess) return hip_status(e, who);
-    }
-    if (need_s) {
-      const hipError_t e = dev_shuffle_run(h, PERC_SITE, ntrials, site_src, nullptr, nullptr);
-      if (e != hipSuccess) return hip_status(e, who);
-    }
-    return batch_run_items_kind(h, kind, cur_rule, nullptr, nullptr, nitems, item_trial, item_nsites,
-                                item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, site_src,
-                                bond_src, wts, fld);
-  }
-  int rc = need_b ? batch_upload_orders(h, ntrials, bond_src) : PERC_OK;
-  if (!rc && need_s) rc = batch_upload_site_orders(h, ntrials, site_src);
-  if (rc) return rc;
-  return batch_run_items_kind(h, kind, cur_rule, site_src, bond_src, nitems, item_trial, item_nsites,
-                              item_nbonds, solve, true, Va, g0, leak, itol, tol, itmax, out, nullptr, nullptr,
-                              wts, fld);
+  BatchSources src;
+  src.seeded = seeded;
+  src.site_src = site_src;
+  src.bond_src = bond_src;
+  return batch_run_items_kind(h, kind, ntrials, src, nitems, item_trial, item_nsites, item_nbonds, sv, out, wts,
+                              fld);
+}
+
+int perc_batch_bondc(perc_ctx* h, int ntrials, const int* orders, int nitems, const int* item_trial,
+                     const int* item_count, int solve, double Va, double g0, double leak, int itol,
+                     double tol, int itmax, perc_batch_item* out) {
+  if (!h || ntrials < 0 || nitems < 0 || (ntrials && !orders) ||
+      (nitems && (!item_trial || !item_count || !out)) || itmax < 0)
+    return PERC_EINVAL;
+  return batch_cond_impl("perc_batch_bondc", false, h, PERC_BOND, PERC_RULE_BOND, ntrials, nullptr, orders,
+                         nitems, item_trial, nullptr, item_count,
+                         BatchSolve{solve, PERC_CUR_FORTRAN, Va, g0, leak, itol, tol, itmax}, out, nullptr,
+                         nullptr, true);
 }
 
 int perc_batch_cond(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials, const int* site_orders,
                     const int* bond_orders, int nitems, const int* item_trial, const int* item_nsites,
                     const int* item_nbonds, int solve, double Va, double g0, double leak, int itol,
                     double tol, int itmax, perc_batch_item* out) {
-  return batch_cond_impl("perc_batch_cond", false, h, kind, rule, cur_rule, ntrials, site_orders,
-                         bond_orders, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
-                         itol, tol, itmax, out);
+  return batch_cond_impl("perc_batch_cond", false, h, kind, rule, ntrials, site_orders, bond_orders, nitems,
+                         item_trial, item_nsites, item_nbonds,
+                         BatchSolve{solve, cur_rule, Va, g0, leak, itol, tol, itmax}, out);
 }
 
 int perc_batch_cond_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials,
@@ -603,9 +579,9 @@ int perc_batch_cond_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int nt
                            const int* item_trial, const int* item_nsites, const int* item_nbonds,
                            int solve, double Va, double g0, double leak, int itol, double tol, int itmax,
                            perc_batch_item* out) {
-  return batch_cond_impl("perc_batch_cond_seeded", true, h, kind, rule, cur_rule, ntrials, site_seeds,
-                         bond_seeds, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
-                         itol, tol, itmax, out);
+  return batch_cond_impl("perc_batch_cond_seeded", true, h, kind, rule, ntrials, site_seeds, bond_seeds, nitems,
+                         item_trial, item_nsites, item_nbonds,
+                         BatchSolve{solve, cur_rule, Va, g0, leak, itol, tol, itmax}, out);
 }
 
 int perc_batch_currents_supported(int kind, int lattice, int m, int n, int pbc) {
@@ -617,13 +593,10 @@ int perc_batch_cond_currents(perc_ctx* h, int kind, int rule, int cur_rule, int 
                              const int* item_trial, const int* item_nsites, const int* item_nbonds,
                              double Va, double g0, double leak, int itol, double tol, int itmax,
                              perc_batch_item* out, double cut, perc_batch_currents* cur, double* vint_out) {
-  BatchFields fld;
-  fld.cut = cut;
-  fld.cur = cur;
-  fld.vint = vint_out;
-  return batch_cond_impl("perc_batch_cond_currents", false, h, kind, rule, cur_rule, ntrials, site_orders,
-                         bond_orders, nitems, item_trial, item_nsites, item_nbonds, 1, Va, g0, leak, itol, tol,
-                         itmax, out, nullptr, &fld);
+  const BatchFields fld{cut, cur, vint_out};
+  return batch_cond_impl("perc_batch_cond_currents", false, h, kind, rule, ntrials, site_orders, bond_orders,
+                         nitems, item_trial, item_nsites, item_nbonds,
+                         BatchSolve{1, cur_rule, Va, g0, leak, itol, tol, itmax}, out, nullptr, &fld);
 }
 
 int perc_batch_cond_currents_seeded(perc_ctx* h, int kind, int rule, int cur_rule, int ntrials,
@@ -632,13 +605,10 @@ int perc_batch_cond_currents_seeded(perc_ctx* h, int kind, int rule, int cur_rul
                                     double Va, double g0, double leak, int itol, double tol, int itmax,
                                     perc_batch_item* out, double cut, perc_batch_currents* cur,
                                     double* vint_out) {
-  BatchFields fld;
-  fld.cut = cut;
-  fld.cur = cur;
-  fld.vint = vint_out;
-  return batch_cond_impl("perc_batch_cond_currents_seeded", true, h, kind, rule, cur_rule, ntrials, site_seeds,
-                         bond_seeds, nitems, item_trial, item_nsites, item_nbonds, 1, Va, g0, leak, itol, tol,
-                         itmax, out, nullptr, &fld);
+  const BatchFields fld{cut, cur, vint_out};
+  return batch_cond_impl("perc_batch_cond_currents_seeded", true, h, kind, rule, ntrials, site_seeds, bond_seeds,
+                         nitems, item_trial, item_nsites, item_nbonds,
+                         BatchSolve{1, cur_rule, Va, g0, leak, itol, tol, itmax}, out, nullptr, &fld);
 }
 
 int perc_current_stats_host(int lattice, int m, int n, int pbc, const unsigned char* conducting,
@@ -714,9 +684,9 @@ int perc_batch_cond_weighted(perc_ctx* h, int kind, int rule, int cur_rule, int 
   wts.weights = weights;
   wts.item_wset = item_wset;
   wts.item_wseed = item_wseed;
-  return batch_cond_impl("perc_batch_cond_weighted", false, h, kind, rule, cur_rule, ntrials, site_orders,
-                         bond_orders, nitems, item_trial, item_nsites, item_nbonds, solve, Va, g0, leak,
-                         itol, tol, itmax, out, &wts);
+  return batch_cond_impl("perc_batch_cond_weighted", false, h, kind, rule, ntrials, site_orders, bond_orders,
+                         nitems, item_trial, item_nsites, item_nbonds,
+                         BatchSolve{solve, cur_rule, Va, g0, leak, itol, tol, itmax}, out, &wts);
 }
 
 int perc_batch_twister(perc_ctx* h, int nseeds, const unsigned int* seeds, long long n, double* out) {
@@ -793,44 +763,31 @@ static int batch_scan_impl(const char* who, bool seeded, perc_ctx* h, int kind, 
     return bad("scan PERC_BOND or PERC_SITE only");
   if (ntrials < 0) return bad("ntrials < 0");
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
-  const int t = h->g.t, nb = (int)h->nb;
-  if (seeded && ((need_s && !shuffle_supported(t)) || (need_b && !shuffle_supported(nb))))
-    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (seeded && !shuffle_lists_ok(h, kind)) return bad(kShuffleReach);
   if (ntrials == 0) return PERC_OK;
   if ((need_s && !site_src) || (need_b && !bond_src) || !out)
     return bad(seeded ? "a seed list the kind reads (or out) is missing"
                       : "an order list the kind reads (or out) is missing");
   if (kind == PERC_SITEBOND) {
     if (!fixed) return bad("PERC_SITEBOND needs fixed[ntrials]");
-    const int cap = scan == PERC_BOND ? t : nb;
+    const int cap = scan == PERC_BOND ? h->g.t : (int)h->nb;
     for (int i = 0; i < ntrials; ++i)
       if (fixed[i] < 0 || fixed[i] > cap)
         return bad("fixed outside 0..t (scan PERC_BOND) / 0..nb (scan PERC_SITE)");
   }
   hipSetDevice(h->device);
-  // launches whose rank arrays stay under 64 MB of device memory
-  const long long per = 4LL * ((need_s ? t : 0) + (need_b ? nb : 0));
-  const int chunk = (int)std::max(1LL, std::min<long long>(ntrials, (64LL << 20) / per));
-  std::vector<int> rank_s(need_s && !seeded ? (size_t)chunk * t : 0);
-  std::vector<int> rank_b(need_b && !seeded ? (size_t)chunk * nb : 0);
-  for (int i0 = 0; i0 < ntrials; i0 += chunk) {
-    const int k = std::min(chunk, ntrials - i0);
-    const int* fx = kind == PERC_SITEBOND ? fixed + i0 : nullptr;
-    hipError_t e = hipSuccess;
-    if (seeded) {
-      // the chunk's ranks straight into the batch path's buffers, the scan over them
-      if (need_s) e = dev_shuffle_run(h, PERC_SITE, k, site_src + i0, nullptr, nullptr);
-      if (e == hipSuccess && need_b) e = dev_shuffle_run(h, PERC_BOND, k, bond_src + i0, nullptr, nullptr);
-      int have_s = 0, have_b = 0;
-      const int* d_s = need_s ? dev_batch_site_ranks(h, &have_s) : nullptr;
-      const int* d_b = need_b ? dev_batch_ranks(h, &have_b) : nullptr;
-      if (e == hipSuccess) e = dev_scan_run(h, kind, scan, k, d_s, d_b, fx, out + i0);
-    } else {
-      if (need_s) order_ranks(k, t, site_src + (size_t)i0 * (t + 1), rank_s.data());
-      if (need_b) order_ranks(k, nb, bond_src + (size_t)i0 * (nb + 1), rank_b.data());
-      e = dev_scan_upload_run(h, kind, scan, k, need_s ? rank_s.data() : nullptr,
-                              need_b ? rank_b.data() : nullptr, fx, out + i0);
-    }
+  BatchSources src;
+  src.seeded = seeded;
+  src.site_src = site_src;
+  src.bond_src = bond_src;
+  // a trial is an item: runs of consecutive trials whose rank arrays stay under 64 MB
+  ItemRuns runs(nullptr, ntrials, ntrials, (int)std::min<long long>(ntrials, rank_run_cap(h, kind)));
+  while (runs.next()) {
+    const int i0 = runs.i0, k = runs.n;
+    const int *d_s = nullptr, *d_b = nullptr;
+    hipError_t e = provide_ranks(h, kind, src, i0, nullptr, k, &d_s, &d_b);
+    if (e == hipSuccess)
+      e = dev_scan_run(h, kind, scan, k, d_s, d_b, kind == PERC_SITEBOND ? fixed + i0 : nullptr, out + i0);
     if (e != hipSuccess) return hip_status(e, who);
   }
   return PERC_OK;
@@ -856,9 +813,7 @@ int perc_batch_clusters_supported(int lattice, int m, int n, int pbc, int nexact
 
 // perc_batch_clusters (seeded = false: site_src / bond_src are order lists)
 // and perc_batch_clusters_seeded (true: seed lists, the orders shuffled on the
-// device).  A launch takes a run of items and the trials they name, numbered
-// afresh in order of first use: a run of k items names at most k trials, so
-// the bound on the run bounds the launch's rank arrays too.
+// device)
 static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int kind, int ntrials,
                                const int* site_src, const int* bond_src, int nitems, const int* item_trial,
                                const int* item_nsites, const int* item_nbonds, int nexact,
@@ -875,72 +830,28 @@ static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int ki
   if (!clusters_supported(h->g, nexact))
     return bad("lattice not supported by the cluster kernel (perc_batch_clusters_supported)");
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
-  if (ntrials && ((need_s && !site_src) || (need_b && !bond_src)))
-    return bad(seeded ? "a seed list the kind reads is missing" : "an order list the kind reads is missing");
-  if (nitems && (!item_trial || !out || (need_s && !item_nsites) || (need_b && !item_nbonds)))
-    return bad("item_trial, out or a count list the kind reads is missing");
-  const int t = h->g.t, nb = (int)h->nb;
-  for (int i = 0; i < nitems; ++i) {
-    if (item_trial[i] < 0 || item_trial[i] >= ntrials) return bad("item_trial outside 0..ntrials-1");
-    if (need_s && (item_nsites[i] < 0 || item_nsites[i] > t + 1)) return bad("item_nsites outside 0..t+1");
-    if (need_b && (item_nbonds[i] < 0 || item_nbonds[i] > nb + 1)) return bad("item_nbonds outside 0..nb+1");
-  }
-  if (seeded && ((need_s && !shuffle_supported(t)) || (need_b && !shuffle_supported(nb))))
-    return bad("a list too long for the device shuffle (perc_shuffle_device_supported)");
+  if (const char* text = check_items(need_s, need_b, seeded, ntrials, site_src, bond_src, nitems, item_trial,
+                                     item_nsites, item_nbonds, out, h->g.t, (int)h->nb))
+    return bad(text);
+  if (seeded && !shuffle_lists_ok(h, kind)) return bad(kShuffleReach);
   if (nitems == 0) return PERC_OK;
   hipSetDevice(h->device);
-  // launches whose rank arrays and histogram rows each stay under 64 MB
-  const long long per = 4LL * ((need_s ? t : 0) + (need_b ? nb : 0));
+  BatchSources src;
+  src.seeded = seeded;
+  src.site_src = site_src;
+  src.bond_src = bond_src;
+  // runs whose rank arrays and histogram rows each stay under 64 MB
   const long long nh = (long long)nexact + 32;
-  const int chunk = (int)std::max(1LL, std::min({(long long)nitems, (64LL << 20) / per, (64LL << 20) / (4 * nh)}));
-  std::vector<int> local((size_t)ntrials, -1), used, ltrial((size_t)chunk), seeds_s, seeds_b;
-  for (int i0 = 0; i0 < nitems; i0 += chunk) {
-    const int n = std::min(chunk, nitems - i0);
-    for (int tr : used) local[tr] = -1;
-    used.clear();
-    for (int i = 0; i < n; ++i) {
-      const int tr = item_trial[i0 + i];
-      if (local[tr] < 0) {
-        local[tr] = (int)used.size();
-        used.push_back(tr);
-      }
-      ltrial[i] = local[tr];
-    }
-    const int k = (int)used.size();
-    const int* ns = need_s ? item_nsites + i0 : nullptr;
-    const int* nbc = need_b ? item_nbonds + i0 : nullptr;
-    int* hrow = hist ? hist + (size_t)i0 * nh : nullptr;
-    hipError_t e = hipSuccess;
-    if (seeded) {
-      // the run's trials shuffled straight into the batch path's rank buffers
-      if (need_s) {
-        seeds_s.resize(k);
-        for (int j = 0; j < k; ++j) seeds_s[j] = site_src[used[j]];
-        e = dev_shuffle_run(h, PERC_SITE, k, seeds_s.data(), nullptr, nullptr);
-      }
-      if (e == hipSuccess && need_b) {
-        seeds_b.resize(k);
-        for (int j = 0; j < k; ++j) seeds_b[j] = bond_src[used[j]];
-        e = dev_shuffle_run(h, PERC_BOND, k, seeds_b.data(), nullptr, nullptr);
-      }
-      int have_s = 0, have_b = 0;
-      const int* d_s = need_s ? dev_batch_site_ranks(h, &have_s) : nullptr;
-      const int* d_b = need_b ? dev_batch_ranks(h, &have_b) : nullptr;
-      if (e == hipSuccess)
-        e = dev_clusters_run(h, kind, n, d_s, d_b, ltrial.data(), ns, nbc, nexact, out + i0, hrow);
-    } else {
-      int *rank_s = nullptr, *rank_b = nullptr;
-      e = dev_clusters_stage(h, need_s ? (size_t)k * t : 0, need_b ? (size_t)k * nb : 0, &rank_s, &rank_b);
-      if (e != hipSuccess) return hip_status(e, who);
-      if (need_s)
-        for (int j = 0; j < k; ++j)
-          order_ranks(1, t, site_src + (size_t)used[j] * (t + 1), rank_s + (size_t)j * t);
-      if (need_b)
-        for (int j = 0; j < k; ++j)
-          order_ranks(1, nb, bond_src + (size_t)used[j] * (nb + 1), rank_b + (size_t)j * nb);
-      e = dev_clusters_upload_run(h, kind, k, need_s ? rank_s : nullptr, need_b ? rank_b : nullptr, n,
-                                  ltrial.data(), ns, nbc, nexact, out + i0, hrow);
-    }
+  ItemRuns runs(item_trial, nitems, ntrials,
+                (int)std::min({(long long)nitems, rank_run_cap(h, kind), (64LL << 20) / (4 * nh)}));
+  while (runs.next()) {
+    const int i0 = runs.i0;
+    const int *d_s = nullptr, *d_b = nullptr;
+    hipError_t e = provide_ranks(h, kind, src, 0, runs.used.data(), (int)runs.used.size(), &d_s, &d_b);
+    if (e == hipSuccess)
+      e = dev_clusters_run(h, kind, runs.n, d_s, d_b, runs.local.data(), need_s ? item_nsites + i0 : nullptr,
+                           need_b ? item_nbonds + i0 : nullptr, nexact, out + i0,
+                           hist ? hist + (size_t)i0 * nh : nullptr);
     if (e != hipSuccess) return hip_status(e, who);
   }
   return PERC_OK;

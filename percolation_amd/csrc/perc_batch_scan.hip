@@ -133,24 +133,9 @@ __global__ __launch_bounds__(NT) void k_batch_scan(ScanArgs a) {
 }
 
 struct ScanState {
-  int* d_rank_s = nullptr;
-  int* d_rank_b = nullptr;
-  size_t cap_s = 0, cap_b = 0;
-  int* d_fixed = nullptr;
-  perc_scan_item* d_out = nullptr;
-  size_t trial_cap = 0;
+  ItemLists<perc_scan_item, 1> trials;  // fixed
   int lds_attr[3][3] = {};  // dynamic LDS granted per instantiation
 };
-
-template <int NT>
-hipError_t launch_kind(ScanState* S, int slot, int kind, const ScanArgs& a, int ntrials, hipStream_t st) {
-  auto launch = [&](auto kd) {
-    return launch_lds(&k_batch_scan<NT, kd()>, &S->lds_attr[slot][kd()], a, ntrials, NT, st, "k_batch_scan");
-  };
-  if (kind == PERC_BOND) return launch(std::integral_constant<int, PERC_BOND>{});
-  if (kind == PERC_SITE) return launch(std::integral_constant<int, PERC_SITE>{});
-  return launch(std::integral_constant<int, PERC_SITEBOND>{});
-}
 
 ScanState* scan_state(perc_ctx* h) {
   if (!h->scan) h->scan = new ScanState();
@@ -162,10 +147,7 @@ ScanState* scan_state(perc_ctx* h) {
 void dev_scan_free(perc_ctx* h) {
   ScanState* S = static_cast<ScanState*>(h->scan);
   if (!S) return;
-  (void)hipFree(S->d_rank_s);
-  (void)hipFree(S->d_rank_b);
-  (void)hipFree(S->d_fixed);
-  (void)hipFree(S->d_out);
+  S->trials.release();
   delete S;
   h->scan = nullptr;
 }
@@ -175,15 +157,7 @@ hipError_t dev_scan_run(perc_ctx* h, int kind, int scan, int ntrials, const int*
   if (ntrials == 0) return hipSuccess;
   ScanState* S = scan_state(h);
   hipStream_t st = h->stream;
-  if (S->trial_cap < (size_t)ntrials) {  // d_fixed and d_out share one capacity
-    size_t cf = 0, co = 0;  // zero on purpose: grow() frees and allocates both afresh
-    S->trial_cap = 0;
-    HIP_TRY(grow(&S->d_fixed, &cf, (size_t)ntrials));
-    HIP_TRY(grow(&S->d_out, &co, (size_t)ntrials));
-    S->trial_cap = ntrials;
-  }
-  if (kind == PERC_SITEBOND)
-    HIP_TRY(hipMemcpyAsync(S->d_fixed, fixed, sizeof(int) * ntrials, hipMemcpyHostToDevice, st));
+  HIP_TRY(S->trials.upload((size_t)ntrials, {kind == PERC_SITEBOND ? fixed : nullptr}, st));
   ScanArgs a;
   a.g = h->g;
   a.nb = (int)h->nb;
@@ -192,31 +166,17 @@ hipError_t dev_scan_run(perc_ctx* h, int kind, int scan, int ntrials, const int*
   a.bond_first = h->d.bond_first;
   a.rank_s = d_rank_s;
   a.rank_b = d_rank_b;
-  a.fixed = S->d_fixed;
+  a.fixed = S->trials.list(0, ntrials);
   a.scan = scan;
-  a.out = S->d_out;
+  a.out = S->trials.d_out;
   a.L = scan_lds(h->g);
-  const int nt = scan_threads(h->g.t);
-  if (nt == 256) HIP_TRY(launch_kind<256>(S, 0, kind, a, ntrials, st));
-  else if (nt == 512) HIP_TRY(launch_kind<512>(S, 1, kind, a, ntrials, st));
-  else HIP_TRY(launch_kind<1024>(S, 2, kind, a, ntrials, st));
-  HIP_TRY(hipMemcpyAsync(out, S->d_out, sizeof(perc_scan_item) * ntrials, hipMemcpyDeviceToHost, st));
+  HIP_TRY(dispatch_threads(scan_threads(h->g.t), [&](auto nt, int slot) {
+    return dispatch_kind_order(kind, false, [&](auto, auto kd) {
+      return launch_lds(&k_batch_scan<nt(), kd()>, &S->lds_attr[slot][kd()], a, ntrials, nt(), st, "k_batch_scan");
+    });
+  }));
+  HIP_TRY(hipMemcpyAsync(out, S->trials.d_out, sizeof(perc_scan_item) * ntrials, hipMemcpyDeviceToHost, st));
   return hipStreamSynchronize(st);  // (fixed and out are the caller's)
-}
-
-hipError_t dev_scan_upload_run(perc_ctx* h, int kind, int scan, int ntrials, const int* rank_s,
-                               const int* rank_b, const int* fixed, perc_scan_item* out) {
-  if (ntrials == 0) return hipSuccess;
-  ScanState* S = scan_state(h);
-  hipStream_t st = h->stream;
-  const size_t ns = rank_s ? (size_t)ntrials * (size_t)h->g.t : 0;
-  const size_t nbk = rank_b ? (size_t)ntrials * (size_t)h->nb : 0;
-  HIP_TRY(grow(&S->d_rank_s, &S->cap_s, ns));
-  HIP_TRY(grow(&S->d_rank_b, &S->cap_b, nbk));
-  if (ns) HIP_TRY(hipMemcpyAsync(S->d_rank_s, rank_s, sizeof(int) * ns, hipMemcpyHostToDevice, st));
-  if (nbk) HIP_TRY(hipMemcpyAsync(S->d_rank_b, rank_b, sizeof(int) * nbk, hipMemcpyHostToDevice, st));
-  return dev_scan_run(h, kind, scan, ntrials, ns ? S->d_rank_s : nullptr, nbk ? S->d_rank_b : nullptr,
-                      fixed, out);
 }
 
 }  // namespace perc

@@ -408,6 +408,44 @@ hipError_t grow(T** p, size_t* cap, size_t n) {
   return hipSuccess;
 }
 
+// *p (pinned host, capacity *cap) grown to n ints; the contents are not kept
+inline hipError_t grow_pinned(int** p, size_t* cap, size_t n) {
+  if (*cap >= n) return hipSuccess;
+  if (*p) HIP_TRY(hipHostFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(p), sizeof(int) * n, hipHostMallocDefault));
+  *cap = n;
+  return hipSuccess;
+}
+
+// What a batch launch keeps per item on the device: NL lists of n ints each
+// (list j at list(j, n)) and one Out per item, of one shared capacity.
+template <class Out, int NL>
+struct ItemLists {
+  int* d_items = nullptr;
+  Out* d_out = nullptr;
+  size_t cap = 0;
+  int* list(int j, size_t n) const { return d_items + (size_t)j * n; }
+  // room for n items, then the host lists src[j] (a NULL one is left out) copied up on st
+  hipError_t upload(size_t n, const int* const (&src)[NL], hipStream_t st) {
+    if (cap < n) {
+      size_t ci = 0, co = 0;  // zero on purpose: grow() frees and allocates both afresh
+      cap = 0;
+      HIP_TRY(grow(&d_items, &ci, NL * n));
+      HIP_TRY(grow(&d_out, &co, n));
+      cap = n;
+    }
+    for (int j = 0; j < NL; ++j)
+      if (src[j]) HIP_TRY(hipMemcpyAsync(list(j, n), src[j], sizeof(int) * n, hipMemcpyHostToDevice, st));
+    return hipSuccess;
+  }
+  void release() {
+    (void)hipFree(d_items);
+    (void)hipFree(d_out);
+  }
+};
+
 // One launch of nblocks workgroups of nt threads of a kernel whose arena is
 // a.L.total bytes of dynamic LDS, beyond the default limit: *granted is what
 // this instantiation has been granted so far

@@ -263,7 +263,7 @@ struct perc_ctx {
   hipEvent_t ev_next[2] = {nullptr, nullptr};  // klaunch: start/stop of the next CG launch
   perc::KernelTiming timing;
   perc::MarchKnobs knobs;  // as the current dev_solve / dev_bench read them
-  void* batch = nullptr;   // perc_batch_bondc's device buffers (perc_batch.hip), made on first use
+  void* batch = nullptr;   // the batch paths' rank store and the conductance launches' buffers (perc_batch.hip), made on first use
   bool batch_large = false;  // perc_set_batch_large: the batch calls run k_batch_cond_large
   int large_lds[2][3] = {};  // dynamic LDS granted per instantiation of it
   int w_lds[3][2][3] = {};   // ... of k_batch_cond_w (perc_batch_weighted.hip)

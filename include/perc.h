@@ -937,6 +937,61 @@ int perc_batch_clusters_seeded(perc_ctx *h, int kind, int ntrials,
                                const int *item_nbonds, int nexact, perc_cluster_item *out,
                                int *hist);
 
+/* ---- batch cluster geometry (the same kernel, one more record) -------- *
+ * perc_batch_clusters_geom is perc_batch_clusters that also returns the
+ * clusters' radii of gyration and the sums behind the correlation length,
+ * all of it in integers.
+ * Member sites of a cluster: its occupied sites (PERC_SITE, PERC_SITEBOND);
+ * the end sites of its bonds (PERC_BOND).  A mixed-kind lone bond has no
+ * member site and does not enter.  n_c = the number of member sites (the
+ * cluster's `size` for the site kind only).
+ * Integer squared distance d2(i, j) of the sites at (row r, column c),
+ * 0-based, row-major from the bottom row:
+ *   PERC_SQUARE      d2 = dc^2 + dr^2                              unit = 1
+ *   PERC_TRIANGULAR  d2 = 3 dc^2 + dY^2, Y = 2 r - (c & 1)         unit = 4
+ * (odd 0-based columns sit half a spacing lower; 4 x the squared distance:
+ * every bond of an even-m open lattice has d2 = 4).  The positions are (r, c)
+ * whatever the bonds are, so the definition holds for every m.
+ * Per cluster, G_c = sum over member pairs i < j of d2(i, j)
+ *                  = n_c sum_i |r_i|^2 - |sum_i r_i|^2
+ * (on the triangular lattice the second term is 3 (sum c)^2 + (sum Y)^2); it
+ * does not depend on the origin; R_c^2 = G_c / (unit n_c^2).
+ *   xi^2 = 2 (g2 - span_g2) / (unit (n2 - span_n2))
+ *   the largest cluster's R^2 = big_g2 / (unit big_n^2)
+ * rows (optional, 3 x 32 long long per item): for the octave b =
+ * floor(log2 n_c), rows[b] = the number of clusters, rows[32 + b] = sum n_c^2,
+ * rows[64 + b] = sum G_c -- R_s^2(s) and with it the fractal dimension.
+ * An item with no cluster has an all-zero record and all-zero rows.
+ * pbc = 0 only (with the left/right wrap the radius has no single meaning).
+ * Everything else -- items, orders, counts, chunking, errors -- is
+ * perc_batch_clusters'; out and hist are bit for bit what that call gives. */
+typedef struct {
+  int n1;          /* sum of n_c over all clusters */
+  int span_n1;     /* ... over the spanning clusters (k_span_top's rule, as in perc_cluster_item) */
+  int big_root;    /* root (min site id) of the cluster with the most member sites (tie: smallest root), 0 if none */
+  int big_n;       /* its n_c */
+  int root_n;      /* n_c of the cluster perc_cluster_item's span_root names, 0 if none */
+  int pad;
+  long long n2, g2;            /* sum of n_c^2, sum of G_c over all clusters */
+  long long span_n2, span_g2;  /* the same over the spanning clusters */
+  long long big_g2;            /* G_c of the largest cluster */
+  long long root_g2;           /* G_c of the span_root cluster, 0 if none */
+} perc_cluster_geom;
+/* host-only: perc_batch_clusters_supported with pbc == 0 */
+int perc_batch_geometry_supported(int lattice, int m, int n, int pbc, int nexact);
+int perc_batch_clusters_geom(perc_ctx *h, int kind, int ntrials,
+                             const int *site_orders, const int *bond_orders,
+                             int nitems, const int *item_trial, const int *item_nsites,
+                             const int *item_nbonds, int nexact, perc_cluster_item *out,
+                             int *hist /* nitems x (nexact+32), or NULL */,
+                             perc_cluster_geom *geom,
+                             long long *rows /* nitems x 96, or NULL */);
+int perc_batch_clusters_geom_seeded(perc_ctx *h, int kind, int ntrials,
+                                    const int *site_seeds, const int *bond_seeds,
+                                    int nitems, const int *item_trial, const int *item_nsites,
+                                    const int *item_nbonds, int nexact, perc_cluster_item *out,
+                                    int *hist, perc_cluster_geom *geom, long long *rows);
+
 /* ---- batch current distributions (one workgroup per item) ------------- *
  * perc_batch_cond returns Gtop and Gbot and drops the voltages between them.
  * perc_batch_cond_currents is perc_batch_cond (it always solves) that also

@@ -73,6 +73,22 @@ CLUSTER_DTYPE = np.dtype([("nclusters", np.int32), ("nlone", np.int32), ("nspan"
 assert CLUSTER_DTYPE.itemsize == C.sizeof(ClusterItem) == 56
 
 
+class ClusterGeom(C.Structure):
+    _fields_ = [("n1", C.c_int), ("span_n1", C.c_int), ("big_root", C.c_int), ("big_n", C.c_int),
+                ("root_n", C.c_int), ("pad", C.c_int), ("n2", C.c_longlong), ("g2", C.c_longlong),
+                ("span_n2", C.c_longlong), ("span_g2", C.c_longlong), ("big_g2", C.c_longlong),
+                ("root_g2", C.c_longlong)]
+
+
+# perc_cluster_geom as a numpy record (Context.batch_clusters(geometry=True), api.cluster_geometry_host)
+GEOM_DTYPE = np.dtype([("n1", np.int32), ("span_n1", np.int32), ("big_root", np.int32), ("big_n", np.int32),
+                       ("root_n", np.int32), ("pad", np.int32), ("n2", np.int64), ("g2", np.int64),
+                       ("span_n2", np.int64), ("span_g2", np.int64), ("big_g2", np.int64),
+                       ("root_g2", np.int64)])
+assert GEOM_DTYPE.itemsize == C.sizeof(ClusterGeom) == 72
+GEOM_ROW = 96  # an item's octave rows: 32 counts, 32 sums of n_c^2, 32 sums of G_c
+
+
 # perc_batch_currents as a numpy record (Context.batch_cond(currents=True), api.current_stats_host)
 CURRENTS_DTYPE = np.dtype([("nbonds", np.int32), ("nabove", np.int32), ("imax", np.float64),
                            ("s1", np.float64), ("s2", np.float64), ("s4", np.float64), ("s6", np.float64),
@@ -233,6 +249,11 @@ SIGNATURES = {
                                       _VP]),
     "perc_batch_clusters_seeded": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int,
                                              _VP, _VP]),
+    "perc_batch_geometry_supported": (C.c_int, [C.c_int] * 5),
+    "perc_batch_clusters_geom": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int, _VP,
+                                           _VP, _VP, _VP]),
+    "perc_batch_clusters_geom_seeded": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP,
+                                                  C.c_int, _VP, _VP, _VP, _VP]),
     "perc_batch_currents_supported": (C.c_int, [C.c_int] * 5),
     "perc_batch_cond_currents": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP,
                                            _VP, _VP, C.c_double, C.c_double, C.c_double, C.c_int,

@@ -157,6 +157,13 @@ def batch_clusters_supported(lattice, m, n, pbc=0, nexact=0):
     return bool(L.lib().perc_batch_clusters_supported(lattice, m, n, pbc, int(nexact)))
 
 
+def batch_geometry_supported(lattice, m, n, pbc=0, nexact=0):
+    """perc_batch_geometry_supported (host-only): True when
+    Context.batch_clusters(geometry=True) can run this lattice --
+    batch_clusters_supported with pbc == 0."""
+    return bool(L.lib().perc_batch_geometry_supported(lattice, m, n, pbc, int(nexact)))
+
+
 def batch_currents_supported(kind, lattice, m, n, pbc=0):
     """perc_batch_currents_supported (host-only): True when
     Context.batch_cond(currents=True) can run this kind on this lattice --
@@ -283,6 +290,83 @@ def cluster_stats_host(lattice, m, n, pbc, kind, site_order=None, nsites=0, bond
         np.add.at(hist, s[s <= nexact] - 1, 1)
         np.add.at(hist, nexact + np.frexp(s)[1].astype(np.int64) - 1, 1)  # floor(log2 s), exactly
     return rec, hist
+
+
+def site_positions(lattice, m, n):
+    """The integer embedding of include/perc.h's cluster geometry: (x, y, wx,
+    unit) with d2(i, j) = wx (x_i - x_j)^2 + (y_i - y_j)^2 = unit x the squared
+    distance of sites i and j (0-based, row-major from the bottom row) --
+    square: x = column, y = row, wx = 1, unit = 1; triangular: y = 2 row -
+    (column & 1), wx = 3, unit = 4."""
+    s = np.arange(m * n, dtype=np.int64)
+    r, c = s // m, s % m
+    if lattice == L.TRIANGULAR:
+        return c, 2 * r - (c & 1), 3, 4
+    return c, r, 1, 1
+
+
+def cluster_geometry_host(lattice, m, n, pbc, kind, site_order=None, nsites=0, bond_order=None, nbonds=0,
+                          nexact=0):
+    """The geometry record and octave rows of Context.batch_clusters(geometry=
+    True) for one item, on the host (no device): from replay_labels' label
+    arrays -- a cluster's member sites are the sites that carry its label
+    (SITE, SITEBOND) or the end sites of the bonds that do (BOND), G_c = n_c
+    sum |r_i|^2 - |sum r_i|^2 over site_positions in int64, spanning as in
+    cluster_stats_host.  pbc = 0 only; nexact is not read (cluster_stats_host's
+    arguments).  Returns (record, rows): a GEOM_DTYPE scalar and 96 int64."""
+    kind = int(kind)
+    if kind not in (L.BOND, L.SITE, L.SITEBOND):
+        raise ValueError("cluster_geometry_host: kind BOND, SITE or SITEBOND")
+    if pbc != 0:
+        raise ValueError("cluster_geometry_host: pbc = 0 only")
+    t = m * n
+    b1, b2 = bond_list(lattice, m, n, pbc)
+    so, ns = _whole_prefix(site_order if kind != L.BOND else None, nsites, t)
+    bo, nbo = _whole_prefix(bond_order if kind != L.SITE else None, nbonds, len(b1))
+    r = replay_labels(lattice, m, n, pbc, kind, site_order=so, nsites=ns, bond_order=bo, nbond=nbo)
+    if kind == L.BOND:  # every occupied bond of a site carries one label
+        lab = np.zeros(t + 1, dtype=np.int64)
+        bl = r["bond_label"].astype(np.int64)
+        lab[b1[bl > 0]] = bl[bl > 0]
+        lab[b2[bl > 0]] = bl[bl > 0]
+        lab = lab[1:]
+    else:
+        lab = r["site_label"].astype(np.int64)
+    nlab = int(lab.max()) + 1 if t else 1
+    x, y, wx, _ = site_positions(lattice, m, n)
+
+    def per_label(w):
+        out = np.zeros(nlab, dtype=np.int64)
+        np.add.at(out, lab, w)
+        out[0] = 0  # (label 0: no member site)
+        return out
+
+    nc = per_label(np.ones(t, dtype=np.int64))
+    sx, sy = per_label(x), per_label(y)
+    G = nc * per_label(wx * x * x + y * y) - wx * sx * sx - sy * sy
+    minsite = np.full(nlab, t + 1, dtype=np.int64)
+    np.minimum.at(minsite, lab, np.arange(1, t + 1))
+    bot, top = np.zeros(nlab, dtype=bool), np.zeros(nlab, dtype=bool)
+    bot[lab[:m]] = True
+    top[lab[t - m:]] = True
+    labels = np.nonzero(nc)[0]
+    span = labels[bot[labels] & top[labels]]
+    rec = np.zeros((), dtype=L.GEOM_DTYPE)
+    rows = np.zeros(L.GEOM_ROW, dtype=np.int64)
+    if len(labels):
+        n_, g_ = nc[labels], G[labels]
+        rec["n1"], rec["n2"], rec["g2"] = n_.sum(), (n_ * n_).sum(), g_.sum()
+        rec["span_n1"], rec["span_n2"], rec["span_g2"] = nc[span].sum(), (nc[span] ** 2).sum(), G[span].sum()
+        big = labels[np.lexsort((minsite[labels], -n_))[0]]  # the most member sites; tie: the smallest root
+        rec["big_root"], rec["big_n"], rec["big_g2"] = minsite[big], nc[big], G[big]
+        if len(span):
+            first = span[np.argmin(minsite[span])]
+            rec["root_n"], rec["root_g2"] = nc[first], G[first]
+        b = np.frexp(n_)[1].astype(np.int64) - 1  # floor(log2 n_c), exactly
+        np.add.at(rows, b, 1)
+        np.add.at(rows, 32 + b, n_ * n_)
+        np.add.at(rows, 64 + b, g_)
+    return rec, rows
 
 
 def _device_shuffle_ok(ctx, kind):
@@ -760,7 +844,8 @@ class Context:
         return [{k: getattr(out[i], k) for k, _ in L.ScanItem._fields_} for i in range(ntrials)]
 
     def batch_clusters(self, kind, item_trial, site_orders=None, bond_orders=None, item_nsites=None,
-                       item_nbonds=None, nexact=0, site_seeds=None, bond_seeds=None, hist=True):
+                       item_nbonds=None, nexact=0, site_seeds=None, bond_seeds=None, hist=True, geometry=False,
+                       geometry_rows=True):
         """perc_batch_clusters: the cluster table's statistics of many small
         (trial, nsites, nbonds) items in one launch, one workgroup each -- the
         items, orders and counts of batch_cond.  Returns (records, hist): a
@@ -770,7 +855,13 @@ class Context:
         hist[i, nexact + floor(log2 s)] every cluster (hist=False: no rows
         are formed, None).  site_seeds / bond_seeds (one seed per trial) in
         place of the order lists: perc_batch_clusters_seeded, the orders
-        shuffled on the device -- the same records."""
+        shuffled on the device -- the same records.  geometry=True
+        (perc_batch_clusters_geom, pbc = 0): returns (records, hist, geom,
+        rows) -- records and hist as without it, geom a GEOM_DTYPE array (n1,
+        n2, g2, the spanning clusters' span_n1, span_n2, span_g2, the largest
+        cluster's big_root, big_n, big_g2, the span_root cluster's root_n,
+        root_g2) and rows the (nitems, 96) int64 octave rows (count, sum
+        n_c^2, sum G_c per floor(log2 n_c); geometry_rows=False: None)."""
         kind, nexact = int(kind), int(nexact)
         it = np.ascontiguousarray(item_trial, dtype=np.int32).reshape(-1)
         so, bo, ntrials, seeded = self._trial_lists(site_orders, bond_orders, site_seeds, bond_seeds)
@@ -779,6 +870,15 @@ class Context:
         it, ns, nbc = self._item_lists(it, item_nsites, item_nbonds)
         out = np.zeros(max(len(it), 1), dtype=L.CLUSTER_DTYPE)
         hrows = np.zeros((max(len(it), 1), max(nexact, 0) + 32), dtype=np.int32) if hist else None
+        if geometry:
+            geom = np.zeros(max(len(it), 1), dtype=L.GEOM_DTYPE)
+            grows = np.zeros((max(len(it), 1), L.GEOM_ROW), dtype=np.int64) if geometry_rows else None
+            name = "perc_batch_clusters_geom_seeded" if seeded else "perc_batch_clusters_geom"
+            L.check(getattr(L.lib(), name)(self.h, kind, ntrials, L.ptr(so), L.ptr(bo), len(it), L.ptr(it),
+                                           L.ptr(ns), L.ptr(nbc), nexact, L.ptr(out), L.ptr(hrows), L.ptr(geom),
+                                           L.ptr(grows)), name)
+            return (out[:len(it)], (hrows[:len(it)] if hist else None), geom[:len(it)],
+                    (grows[:len(it)] if geometry_rows else None))
         name = "perc_batch_clusters_seeded" if seeded else "perc_batch_clusters"
         L.check(getattr(L.lib(), name)(self.h, kind, ntrials, L.ptr(so), L.ptr(bo), len(it), L.ptr(it),
                                        L.ptr(ns), L.ptr(nbc), nexact, L.ptr(out), L.ptr(hrows)), name)
@@ -1468,12 +1568,25 @@ def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5
     fields); stats (npts, 8) int64 {count, sum nclusters, count spanning, sum
     span_size, sum s1, sum s2, sum span_s1, sum span_s2}; hist (npts, nexact +
     32) int64, the items' histogram rows summed over the trials."""
+    return _cluster_curve("cluster_curve", False, lattice, m, n, pbc, kind, grid, master, numtrials, batch, nexact,
+                          device_shuffle, ctx, device)[:3]
+
+
+GEOM_SUMS = ("n1", "n2", "g2", "span_n1", "span_n2", "span_g2", "big_n", "big_g2")
+
+
+def _cluster_curve(who, geometry, lattice, m, n, pbc, kind, grid, master, numtrials, batch, nexact, device_shuffle,
+                   ctx, device):
+    """cluster_curve and, geometry=True, correlation_curve: (trials, stats,
+    hist, gsums, grows) -- the last two None without geometry"""
     if kind not in (L.BOND, L.SITE, L.SITEBOND):
-        raise ValueError("cluster_curve: kind BOND, SITE or SITEBOND")
+        raise ValueError("%s: kind BOND, SITE or SITEBOND" % who)
     if numtrials < 0:
         raise ValueError("numtrials < 0")
     if ctx is not None:
         lattice, m, n, pbc = ctx.lattice, ctx.m, ctx.n, ctx.pbc
+    if geometry and pbc != 0:
+        raise ValueError("%s: pbc = 0 only" % who)
     mixed = kind == L.SITEBOND
     need_s, need_b = kind != L.BOND, kind != L.SITE
     t, nb = m * n, nbonds(lattice, m, n, pbc)
@@ -1488,7 +1601,8 @@ def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5
         ss, bs = trial_seeds(master, max(numtrials, 1)), None
     else:
         ss, bs = None, trial_seeds(master, max(numtrials, 1))
-    batched = batch > 0 and npts > 0 and numtrials > 0 and batch_clusters_supported(lattice, m, n, pbc, nexact)
+    supported = batch_geometry_supported if geometry else batch_clusters_supported
+    batched = batch > 0 and npts > 0 and numtrials > 0 and supported(lattice, m, n, pbc, nexact)
     own = batched and ctx is None
     if own:
         ctx = Context(lattice, m, n, pbc, device)
@@ -1497,6 +1611,9 @@ def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5
         seeded = batched and device_shuffle and _device_shuffle_ok(ctx, kind)
         stats = np.zeros((npts, 8), dtype=np.int64)
         hist = np.zeros((npts, nexact + 32), dtype=np.int64)
+        gsums = np.zeros((npts, 1 + len(GEOM_SUMS) + 1), dtype=np.int64) if geometry else None
+        grows = np.zeros((npts, L.GEOM_ROW), dtype=np.int64) if geometry else None
+        geom = rrows = None
         out = []
         for i0 in range(0, numtrials, group):
             tr = range(i0, min(i0 + group, numtrials))
@@ -1510,18 +1627,26 @@ def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5
                                bond_seeds=bs[tr.start:tr.stop] if need_b else None)
                 else:
                     src = dict(site_orders=so, bond_orders=bo)
-                recs, rows = ctx.batch_clusters(kind, np.repeat(np.arange(len(tr), dtype=np.int32), npts), **src,
-                                                item_nsites=np.tile(cnt_s, len(tr)) if need_s else None,
-                                                item_nbonds=np.tile(cnt_b, len(tr)) if need_b else None,
-                                                nexact=nexact)
+                got = ctx.batch_clusters(kind, np.repeat(np.arange(len(tr), dtype=np.int32), npts), **src,
+                                         item_nsites=np.tile(cnt_s, len(tr)) if need_s else None,
+                                         item_nbonds=np.tile(cnt_b, len(tr)) if need_b else None,
+                                         nexact=nexact, geometry=geometry)
+                recs, rows = got[:2]
+                if geometry:
+                    geom, rrows = got[2:]
             else:
                 recs = np.zeros(len(tr) * npts, dtype=L.CLUSTER_DTYPE)
                 rows = np.zeros((len(tr) * npts, nexact + 32), dtype=np.int32)
+                if geometry:
+                    geom = np.zeros(len(tr) * npts, dtype=L.GEOM_DTYPE)
+                    rrows = np.zeros((len(tr) * npts, L.GEOM_ROW), dtype=np.int64)
                 for k in range(len(tr)):
                     for j in range(npts):
-                        recs[k * npts + j], rows[k * npts + j] = cluster_stats_host(
-                            lattice, m, n, pbc, kind, so[k] if need_s else None, int(cnt_s[j]) if need_s else 0,
-                            bo[k] if need_b else None, int(cnt_b[j]) if need_b else 0, nexact)
+                        item = (lattice, m, n, pbc, kind, so[k] if need_s else None, int(cnt_s[j]) if need_s else 0,
+                                bo[k] if need_b else None, int(cnt_b[j]) if need_b else 0, nexact)
+                        recs[k * npts + j], rows[k * npts + j] = cluster_stats_host(*item)
+                        if geometry:
+                            geom[k * npts + j], rrows[k * npts + j] = cluster_geometry_host(*item)
             for k, ii in enumerate(tr):
                 trows = []
                 for j, (ps, pb) in enumerate(pts):
@@ -1536,16 +1661,51 @@ def cluster_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5
                     stats[j] += (1, r["nclusters"], int(r["nspan"] > 0), r["span_size"], r["s1"], r["s2"],
                                  r["span_s1"], r["span_s2"])
                     hist[j] += rows[k * npts + j]
+                    if geometry:
+                        q = geom[k * npts + j]
+                        row.update({f: int(q[f]) for f in L.GEOM_DTYPE.names if f != "pad"})
+                        gsums[j] += (1,) + tuple(int(q[f]) for f in GEOM_SUMS) + (int(q["big_n"]) ** 2,)
+                        grows[j] += rrows[k * npts + j]
                 trial = dict(ii=ii + 1, rows=trows)
                 if mixed:
                     trial.update(sseed=int(ss[ii]), bseed=int(bs[ii]))
                 else:
                     trial.update(seed=int((ss if need_s else bs)[ii]))
                 out.append(trial)
-        return out, stats, hist
+        return out, stats, hist, gsums, grows
     finally:
         if own:
             ctx.close()
+
+
+def correlation_curve(lattice=0, m=50, n=50, pbc=0, kind=L.BOND, grid=(0.3, 0.4, 0.5, 0.6, 0.7), master=58302,
+                      numtrials=1, batch=256, nexact=64, device_shuffle=False, ctx=None, device=0):
+    """The clusters' geometry as a function of p over trials: the correlation
+    length xi(p), the largest cluster's radius of gyration and R_s^2 per octave
+    of the cluster size (the fractal dimension's data), beside cluster_curve's
+    statistics -- cluster_curve's arguments, seeds, orders and batching, the
+    items through Context.batch_clusters(geometry=True) or, batch=0 or a
+    lattice batch_geometry_supported refuses, through cluster_stats_host and
+    cluster_geometry_host with no device; the same integers either way.
+    pbc = 0 only (ValueError otherwise).  Returns a dict: trials (cluster_curve's,
+    each row with the geometry record's fields too), stats and hist
+    (cluster_curve's), sums (npts, 10) int64 {count, then the trials' sums of
+    n1, n2, g2, span_n1, span_n2, span_g2, big_n, big_g2, big_n^2}, rows (npts,
+    96) int64 the items' octave rows summed, unit (1 square, 4 triangular), and
+    the derived floats xi (npts) = sqrt(2 (g2 - span_g2) / (unit (n2 -
+    span_n2))), big_r2 (npts) = sum big_g2 / (unit sum big_n^2) and rs2 (npts,
+    32) = rows[64 + b] / (unit rows[32 + b]); nan where a denominator is 0."""
+    trials, stats, hist, sums, rows = _cluster_curve("correlation_curve", True, lattice, m, n, pbc, kind, grid, master,
+                                                     numtrials, batch, nexact, device_shuffle, ctx, device)
+    unit = 4 if (ctx.lattice if ctx is not None else lattice) == L.TRIANGULAR else 1
+
+    def ratio(num, den):
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.full(num.shape, np.nan), where=den != 0)
+
+    xi = np.sqrt(ratio(2.0 * (sums[:, 3] - sums[:, 6]), unit * (sums[:, 2] - sums[:, 5])))
+    return dict(trials=trials, stats=stats, hist=hist, sums=sums, rows=rows, unit=unit, xi=xi,
+                big_r2=ratio(sums[:, 8], unit * sums[:, 9]), rs2=ratio(rows[:, 64:], unit * rows[:, 32:64]))
 
 
 # ---------------------------------------------------------------- file output

@@ -323,14 +323,26 @@ constexpr int kClusterLdsStatic = 256;  // the compiler's own static LDS of k_ba
 // host-only check of perc_batch_clusters_supported: the scan's lattices, and
 // 0 <= nexact <= kClusterExactMax
 bool clusters_supported(const Geom& g, int nexact);
+// The geometry instantiations' arena (k_batch_clusters<.., GEOM = true>):
+// cluster_lds, then kGeomWords words of 8 bytes at *oGeo -- the 3 x 32 octave
+// sums of an item's rows, 12 workgroup sums, the largest cluster's key and the
+// spanning root.
+constexpr int kGeomRowWords = 96;
+constexpr int kGeomWords = kGeomRowWords + 16;
+ClusterLds cluster_geom_lds(const Geom& g, int nexact, int* oGeo);
+// host-only check of perc_batch_geometry_supported: clusters_supported, pbc == 0
+bool geometry_supported(const Geom& g, int nexact);
 // device side.  nitems items over rank arrays in device memory (d_rank_b:
 // ntrials x nb, d_rank_s: ntrials x t; either may be NULL where the kind does
 // not read it; every item_trial lies inside them: the caller's check); the
 // item lists, out (nitems) and hist (nitems x (nexact + 32), or NULL) on the
-// host.  Threads per workgroup: scan_threads(t).
+// host.  Threads per workgroup: scan_threads(t).  geom (nitems, host): the
+// launch is the GEOM instantiation's, which also fills rows (nitems x
+// kGeomRowWords, or NULL).
 hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank_s, const int* d_rank_b,
                             const int* item_trial, const int* item_nsites, const int* item_nbonds,
-                            int nexact, perc_cluster_item* out, int* hist);
+                            int nexact, perc_cluster_item* out, int* hist, perc_cluster_geom* geom = nullptr,
+                            long long* rows = nullptr);
 void dev_clusters_free(perc_ctx* h);
 // ---- device shuffle (perc_batch_shuffle.hip: k_shuffle_ranks) -----------
 // Byte offsets of k_shuffle_ranks' LDS arena (every offset a multiple of 16):

@@ -21,7 +21,14 @@
 // The sizes do not depend on the order of occupation.  Spanning is
 // k_span_top's rule, as in k_batch_scan; several clusters may span, the record
 // sums over all of them.
+//
+// The GEOM instantiations go on to the clusters' geometry (include/perc.h,
+// perc_cluster_geom): member sites per root, then the gyration sums
+// G_c = n_c sum |r_i|^2 - |sum r_i|^2 in integers, summed over all clusters,
+// the spanning ones and per octave of n_c, and G_c of the largest cluster and
+// of the span_root cluster -- a few more passes over LDS (cluster_geometry).
 #include <climits>
+#include <type_traits>
 
 #include "perc_batch.h"
 #include "perc_batch_uf.h"
@@ -43,12 +50,187 @@ struct ClusterArgs {
   ClusterLds L;
 };
 
+// ... and what the GEOM instantiations take beside it
+struct ClusterGeomArgs : ClusterArgs {
+  perc_cluster_geom* geom;
+  long long* rows;  // nitems x kGeomRowWords, or NULL
+  int oGeo;         // kGeomWords words of 8 bytes
+};
+
 constexpr int kSums = 7;  // nclusters, nlone, nspan, s1, s2, span_s1, span_s2
+
+// the geometry words: the octave rows at 0, then
+constexpr int kGwSums = kGeomRowWords;  // 12 workgroup sums (cluster_geometry's order)
+constexpr int kGwKey = kGwSums + 12;    // max over the roots of (n_c << 32 | INT_MAX - root)
+constexpr int kGwSpan = kGwKey + 1;     // the record's span_root
+
+// the lanes' v[0..N) summed over the wave, then lane 0's atomicAdd into w[0..N)
+template <int N>
+__device__ __forceinline__ void wave_sums_to_lds(long long (&v)[N], unsigned long long* w) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] += __shfl_xor(v[j], off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) atomicAdd(&w[j], (unsigned long long)v[j]);
+  }
+}
+
+// The geometry record and octave rows of the labeled item (parent[] final
+// roots, link[] bit 7 the site and mixed kinds' member sites, flag[] the
+// spanning roots, gw[0 .. kGwKey] zero, gw[kGwSpan] the record's span_root,
+// written before the barrier this starts with).  size[] and the low link bits
+// are dead by now and reused: size[root] holds n_c, then the clusters' column
+// sums, then their row sums; a root's link byte becomes bit 7 | spanning << 6
+// | octave.  Coordinates: x = column (weight wx = 3 on the triangular lattice,
+// else 1), y = row on the square lattice, 2 row - (column & 1) + 1 >= 0 on the
+// triangular one.  Every product that can pass 2^31 is formed in 64 bits; all
+// sums are integers, so any association gives the same result.  Every barrier
+// is reached by every thread.
+template <int NT, int KIND>
+__device__ __forceinline__ void cluster_geometry(const Geom& g, int item, const int* parent, int* size,
+                                                 uint8_t* link, const uint8_t* flag, unsigned long long* gw,
+                                                 perc_cluster_geom* geom, long long* rows) {
+  const int m = g.m, T = g.t, t = threadIdx.x;
+  const bool tri = g.lattice == kTriangular;
+  const int wx = tri ? 3 : 1;
+  auto coords = [&](int s, int* x, int* y) {
+    const int r = div_m(g, s - 1);
+    *x = s - 1 - r * m;
+    *y = tri ? 2 * r - (*x & 1) + 1 : r;
+  };
+  __syncthreads();  // the record's read of size[], the row's reads of hist[]
+  // bond kind: a member site is an end of an occupied bond -- not a root, or a root with bonds
+  for (int s = t + 1; s <= T; s += NT) {
+    if constexpr (KIND == PERC_BOND) link[s] = (parent[s] != s || size[s] > 0) ? 0x80 : 0;
+    size[s] = 0;
+  }
+  __syncthreads();
+  for (int s = t + 1; s <= T; s += NT)
+    if (link[s] & 0x80) atomicAdd(&size[parent[s]], 1);
+  __syncthreads();
+
+  // ---- the roots: n_c sums, the octave rows' counts, the largest cluster
+  {
+    long long v[4] = {};  // n1, n2, span_n1, span_n2
+    unsigned long long key = 0;
+    for (int s = t + 1; s <= T; s += NT) {
+      if (parent[s] != s || !(link[s] & 0x80)) continue;
+      const int nc = size[s], b = 31 - __builtin_clz((unsigned)nc);  // (nc >= 1)
+      const long long q = (long long)nc * nc;
+      const bool sp = s <= m && flag[s];
+      v[0] += nc;
+      v[1] += q;
+      if (sp) {
+        v[2] += nc;
+        v[3] += q;
+      }
+      atomicAdd(&gw[b], 1ull);
+      atomicAdd(&gw[32 + b], (unsigned long long)q);
+      key = max(key, (unsigned long long)nc << 32 | (unsigned)(INT_MAX - s));
+      link[s] = (uint8_t)(0x80 | (sp ? 0x40 : 0) | b);
+    }
+    wave_sums_to_lds(v, gw + kGwSums);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) key = max(key, __shfl_xor(key, off, 64));
+    if ((t & 63) == 0) atomicMax(&gw[kGwKey], key);
+  }
+  __syncthreads();
+  const unsigned long long top = gw[kGwKey];
+  const int big = top ? INT_MAX - (int)(unsigned)top : 0;
+  const int sroot = (int)gw[kGwSpan];
+  const int big_n = size[big], root_n = size[sroot];  // (size[0] == 0)
+
+  // ---- the sites: sum of n_c |r_i|^2 (all, spanning, per octave: runs of one
+  // octave in a register, one LDS atomic per run), the two named clusters' own sums
+  long long v[8] = {};  // g2, span_g2, then sum |r|^2, sum x, sum y of big and of span_root
+  {
+    int cur = -1;
+    unsigned long long acc = 0;
+    for (int s = t + 1; s <= T; s += NT) {
+      if (!(link[s] & 0x80)) continue;
+      const int root = parent[s];
+      const unsigned lr = link[root];
+      int x, y;
+      coords(s, &x, &y);
+      const int q = wx * x * x + y * y;
+      const long long nq = (long long)size[root] * q;
+      v[0] += nq;
+      if (lr & 0x40) v[1] += nq;
+      const int b = lr & 31;
+      if (b != cur) {
+        if (cur >= 0) atomicAdd(&gw[64 + cur], acc);
+        cur = b;
+        acc = 0;
+      }
+      acc += (unsigned long long)nq;
+      if (root == big) {
+        v[2] += q;
+        v[3] += x;
+        v[4] += y;
+      }
+      if (root == sroot) {
+        v[5] += q;
+        v[6] += x;
+        v[7] += y;
+      }
+    }
+    if (cur >= 0) atomicAdd(&gw[64 + cur], acc);
+  }
+  // ---- minus |sum r_i|^2 per cluster: the column sums, then the row sums
+#pragma unroll 1
+  for (int ax = 0; ax < 2; ++ax) {
+    __syncthreads();  // size[] is read no more
+    for (int s = t + 1; s <= T; s += NT) size[s] = 0;
+    __syncthreads();
+    for (int s = t + 1; s <= T; s += NT) {
+      if (!(link[s] & 0x80)) continue;
+      int x, y;
+      coords(s, &x, &y);
+      atomicAdd(&size[parent[s]], ax ? y : x);
+    }
+    __syncthreads();
+    for (int s = t + 1; s <= T; s += NT) {
+      const unsigned lk = link[s];
+      if (parent[s] != s || !(lk & 0x80)) continue;
+      const long long c = size[s];
+      const long long sq = c * c * (ax ? 1 : wx);
+      v[0] -= sq;
+      if (lk & 0x40) v[1] -= sq;
+      atomicAdd(&gw[64 + (lk & 31)], (unsigned long long)-sq);
+    }
+  }
+  wave_sums_to_lds(v, gw + kGwSums + 4);
+  __syncthreads();
+  if (t == 0) {
+    const long long* w = reinterpret_cast<const long long*>(gw) + kGwSums;
+    perc_cluster_geom o;
+    o.n1 = (int)w[0];
+    o.span_n1 = (int)w[2];
+    o.big_root = big;
+    o.big_n = big_n;
+    o.root_n = root_n;
+    o.pad = 0;
+    o.n2 = w[1];
+    o.g2 = w[4];
+    o.span_n2 = w[3];
+    o.span_g2 = w[5];
+    o.big_g2 = big_n * w[6] - wx * w[7] * w[7] - w[8] * w[8];
+    o.root_g2 = root_n * w[9] - wx * w[10] * w[10] - w[11] * w[11];
+    geom[item] = o;
+  }
+  if (rows) {
+    long long* __restrict__ row = rows + (size_t)item * kGeomRowWords;
+    for (int k = t; k < kGeomRowWords; k += NT) row[k] = (long long)gw[k];
+  }
+}
 
 // NT threads, sites t + 1, t + 1 + NT, .. (at most kScanSPT) per thread.
 // Every loop bound is a kernel argument; lds_label's exit is a workgroup vote.
-template <int NT, int KIND>
-__global__ __launch_bounds__(NT) void k_batch_clusters(ClusterArgs a) {
+template <int NT, int KIND, bool GEOM>
+__global__ __launch_bounds__(NT) void k_batch_clusters(std::conditional_t<GEOM, ClusterGeomArgs, ClusterArgs> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Geom g = a.g;
   const int m = g.m, T = g.t, nexact = a.nexact, nh = a.nexact + 32;
@@ -73,6 +255,10 @@ __global__ __launch_bounds__(NT) void k_batch_clusters(ClusterArgs a) {
   for (int c = t; c <= m; c += NT) flag[c] = 0;
   for (int s = t; s <= T; s += NT) size[s] = 0;
   for (int k = t; k < nh; k += NT) hist[k] = 0;
+  if constexpr (GEOM) {
+    unsigned long long* gw = reinterpret_cast<unsigned long long*>(smem + a.oGeo);
+    for (int k = t; k < kGwSpan; k += NT) gw[k] = 0;
+  }
   __syncthreads();
   // spanning (k_span_top's rule): a root <= m with a member in the top row
   for (int c = t; c < m; c += NT) {
@@ -152,18 +338,27 @@ __global__ __launch_bounds__(NT) void k_batch_clusters(ClusterArgs a) {
     o.span_s1 = sum[5];
     o.span_s2 = sum[6];
     a.out[item] = o;
+    if constexpr (GEOM) reinterpret_cast<unsigned long long*>(smem + a.oGeo)[kGwSpan] = (unsigned long long)root;
   }
   if (a.hist) {
     int* __restrict__ row = a.hist + (size_t)item * nh;
     for (int k = t; k < nh; k += NT) row[k] = hist[k];
   }
+  if constexpr (GEOM)
+    cluster_geometry<NT, KIND>(g, item, parent, size, link, flag,
+                               reinterpret_cast<unsigned long long*>(smem + a.oGeo), a.geom, a.rows);
 }
 
 struct ClusterState {
   ItemLists<perc_cluster_item, 3> items;  // item_trial, then item_nsites, then item_nbonds
   int* d_hist = nullptr;
   size_t hist_cap = 0;
+  perc_cluster_geom* d_geom = nullptr;  // (the GEOM launches' outputs)
+  size_t geom_cap = 0;
+  long long* d_rows = nullptr;
+  size_t rows_cap = 0;
   int lds_attr[3][3] = {};  // dynamic LDS granted per instantiation
+  int lds_attr_g[3][3] = {};
 };
 
 ClusterState* cluster_state(perc_ctx* h) {
@@ -178,13 +373,16 @@ void dev_clusters_free(perc_ctx* h) {
   if (!S) return;
   S->items.release();
   (void)hipFree(S->d_hist);
+  (void)hipFree(S->d_geom);
+  (void)hipFree(S->d_rows);
   delete S;
   h->clusters = nullptr;
 }
 
 hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank_s, const int* d_rank_b,
                             const int* item_trial, const int* item_nsites, const int* item_nbonds,
-                            int nexact, perc_cluster_item* out, int* hist) {
+                            int nexact, perc_cluster_item* out, int* hist, perc_cluster_geom* geom,
+                            long long* rows) {
   if (nitems == 0) return hipSuccess;
   ClusterState* S = cluster_state(h);
   hipStream_t st = h->stream;
@@ -192,7 +390,7 @@ hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank
   if (hist) HIP_TRY(grow(&S->d_hist, &S->hist_cap, n * nh));
   HIP_TRY(S->items.upload(n, {item_trial, kind != PERC_BOND ? item_nsites : nullptr,
                               kind != PERC_SITE ? item_nbonds : nullptr}, st));
-  ClusterArgs a;
+  ClusterGeomArgs a;
   a.g = h->g;
   a.nb = (int)h->nb;
   a.nexact = nexact;
@@ -205,14 +403,36 @@ hipError_t dev_clusters_run(perc_ctx* h, int kind, int nitems, const int* d_rank
   a.out = S->items.d_out;
   a.hist = hist ? S->d_hist : nullptr;
   a.L = cluster_lds(h->g, nexact);
+  a.geom = nullptr;
+  a.rows = nullptr;
+  a.oGeo = 0;
+  if (geom) {
+    // (the kernel writes every item's record and rows; zeroed all the same, so
+    // that nothing of an earlier launch can be read back)
+    HIP_TRY(grow(&S->d_geom, &S->geom_cap, n));
+    HIP_TRY(hipMemsetAsync(S->d_geom, 0, sizeof(perc_cluster_geom) * n, st));
+    if (rows) {
+      HIP_TRY(grow(&S->d_rows, &S->rows_cap, n * kGeomRowWords));
+      HIP_TRY(hipMemsetAsync(S->d_rows, 0, sizeof(long long) * n * kGeomRowWords, st));
+    }
+    a.geom = S->d_geom;
+    a.rows = rows ? S->d_rows : nullptr;
+    a.L = cluster_geom_lds(h->g, nexact, &a.oGeo);
+  }
   HIP_TRY(dispatch_threads(scan_threads(h->g.t), [&](auto nt, int slot) {
     return dispatch_kind_order(kind, false, [&](auto, auto kd) {
-      return launch_lds(&k_batch_clusters<nt(), kd()>, &S->lds_attr[slot][kd()], a, nitems, nt(), st,
-                        "k_batch_clusters");
+      if (geom)
+        return launch_lds(&k_batch_clusters<nt(), kd(), true>, &S->lds_attr_g[slot][kd()], a, nitems, nt(), st,
+                          "k_batch_clusters");
+      return launch_lds(&k_batch_clusters<nt(), kd(), false>, &S->lds_attr[slot][kd()],
+                        static_cast<const ClusterArgs&>(a), nitems, nt(), st, "k_batch_clusters");
     });
   }));
   HIP_TRY(hipMemcpyAsync(out, S->items.d_out, sizeof(perc_cluster_item) * n, hipMemcpyDeviceToHost, st));
   if (hist) HIP_TRY(hipMemcpyAsync(hist, S->d_hist, sizeof(int) * n * nh, hipMemcpyDeviceToHost, st));
+  if (geom) HIP_TRY(hipMemcpyAsync(geom, S->d_geom, sizeof(perc_cluster_geom) * n, hipMemcpyDeviceToHost, st));
+  if (geom && rows)
+    HIP_TRY(hipMemcpyAsync(rows, S->d_rows, sizeof(long long) * n * kGeomRowWords, hipMemcpyDeviceToHost, st));
   return hipStreamSynchronize(st);  // (the item lists and the outputs are the caller's)
 }
 

@@ -5,7 +5,9 @@
 // perc_batch_shuffle, perc_batch_scan_seeded, perc_batch_cond_seeded, and the
 // weighted perc_batch_weighted_supported, perc_batch_cond_weighted,
 // perc_batch_twister, and the cluster tables' perc_batch_clusters_supported,
-// perc_batch_clusters, perc_batch_clusters_seeded, and the current
+// perc_batch_clusters, perc_batch_clusters_seeded, the cluster geometry's
+// perc_batch_geometry_supported, perc_batch_clusters_geom,
+// perc_batch_clusters_geom_seeded, and the current
 // distributions' perc_batch_currents_supported, perc_batch_cond_currents,
 // perc_batch_cond_currents_seeded, perc_current_stats_host):
 // the launch geometry and LDS layouts, then the calls.  Who owns what: every
@@ -206,6 +208,19 @@ ClusterLds cluster_lds(const Geom& g, int nexact) {
 bool clusters_supported(const Geom& g, int nexact) {
   if (nexact < 0 || nexact > kClusterExactMax || !scan_supported(g)) return false;
   return cluster_lds(g, nexact).total + kClusterLdsStatic <= kBatchLdsMax;
+}
+
+ClusterLds cluster_geom_lds(const Geom& g, int nexact, int* oGeo) {
+  ClusterLds L = cluster_lds(g, nexact);
+  *oGeo = L.total;
+  L.total += up16(8LL * kGeomWords);
+  return L;
+}
+
+bool geometry_supported(const Geom& g, int nexact) {
+  if (g.pbc != 0 || !clusters_supported(g, nexact)) return false;
+  int oGeo = 0;
+  return cluster_geom_lds(g, nexact, &oGeo).total + kClusterLdsStatic <= kBatchLdsMax;
 }
 
 ShuffleLds shuffle_lds(int N) {
@@ -813,11 +828,12 @@ int perc_batch_clusters_supported(int lattice, int m, int n, int pbc, int nexact
 
 // perc_batch_clusters (seeded = false: site_src / bond_src are order lists)
 // and perc_batch_clusters_seeded (true: seed lists, the orders shuffled on the
-// device)
+// device); geometry: the _geom forms, which also fill geom and rows (optional)
 static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int kind, int ntrials,
                                const int* site_src, const int* bond_src, int nitems, const int* item_trial,
                                const int* item_nsites, const int* item_nbonds, int nexact,
-                               perc_cluster_item* out, int* hist) {
+                               perc_cluster_item* out, int* hist, bool geometry = false,
+                               perc_cluster_geom* geom = nullptr, long long* rows = nullptr) {
   if (!h) return PERC_EINVAL;
   auto bad = [who](const char* text) {
     set_error(std::string(who) + ": " + text);
@@ -829,6 +845,9 @@ static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int ki
   if (nexact < 0 || nexact > kClusterExactMax) return bad("nexact outside 0..1024");
   if (!clusters_supported(h->g, nexact))
     return bad("lattice not supported by the cluster kernel (perc_batch_clusters_supported)");
+  if (geometry && !geometry_supported(h->g, nexact))
+    return bad("lattice not supported by the cluster geometry: pbc = 0 only (perc_batch_geometry_supported)");
+  if (geometry && nitems && !geom) return bad("geom missing");
   const bool need_s = kind != PERC_BOND, need_b = kind != PERC_SITE;
   if (const char* text = check_items(need_s, need_b, seeded, ntrials, site_src, bond_src, nitems, item_trial,
                                      item_nsites, item_nbonds, out, h->g.t, (int)h->nb))
@@ -840,10 +859,13 @@ static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int ki
   src.seeded = seeded;
   src.site_src = site_src;
   src.bond_src = bond_src;
-  // runs whose rank arrays and histogram rows each stay under 64 MB
+  // runs whose rank arrays and histogram rows (with the geometry's records
+  // and octave rows, where asked) each stay under 64 MB
   const long long nh = (long long)nexact + 32;
+  const long long per_item =
+      4 * nh + (geometry ? (long long)sizeof(perc_cluster_geom) + (rows ? 8LL * kGeomRowWords : 0) : 0);
   ItemRuns runs(item_trial, nitems, ntrials,
-                (int)std::min({(long long)nitems, rank_run_cap(h, kind), (64LL << 20) / (4 * nh)}));
+                (int)std::min({(long long)nitems, rank_run_cap(h, kind), (64LL << 20) / per_item}));
   while (runs.next()) {
     const int i0 = runs.i0;
     const int *d_s = nullptr, *d_b = nullptr;
@@ -851,7 +873,8 @@ static int batch_clusters_impl(const char* who, bool seeded, perc_ctx* h, int ki
     if (e == hipSuccess)
       e = dev_clusters_run(h, kind, runs.n, d_s, d_b, runs.local.data(), need_s ? item_nsites + i0 : nullptr,
                            need_b ? item_nbonds + i0 : nullptr, nexact, out + i0,
-                           hist ? hist + (size_t)i0 * nh : nullptr);
+                           hist ? hist + (size_t)i0 * nh : nullptr, geometry ? geom + i0 : nullptr,
+                           geometry && rows ? rows + (size_t)i0 * kGeomRowWords : nullptr);
     if (e != hipSuccess) return hip_status(e, who);
   }
   return PERC_OK;
@@ -870,6 +893,28 @@ int perc_batch_clusters_seeded(perc_ctx* h, int kind, int ntrials, const int* si
                                perc_cluster_item* out, int* hist) {
   return batch_clusters_impl("perc_batch_clusters_seeded", true, h, kind, ntrials, site_seeds, bond_seeds,
                              nitems, item_trial, item_nsites, item_nbonds, nexact, out, hist);
+}
+
+int perc_batch_geometry_supported(int lattice, int m, int n, int pbc, int nexact) {
+  if (lattice != PERC_SQUARE && lattice != PERC_TRIANGULAR) return 0;
+  if (m < 1 || n < 1 || (long long)m * n > kScanSites) return 0;
+  return geometry_supported(make_geom(lattice, m, n, pbc), nexact) ? 1 : 0;
+}
+
+int perc_batch_clusters_geom(perc_ctx* h, int kind, int ntrials, const int* site_orders, const int* bond_orders,
+                             int nitems, const int* item_trial, const int* item_nsites, const int* item_nbonds,
+                             int nexact, perc_cluster_item* out, int* hist, perc_cluster_geom* geom,
+                             long long* rows) {
+  return batch_clusters_impl("perc_batch_clusters_geom", false, h, kind, ntrials, site_orders, bond_orders, nitems,
+                             item_trial, item_nsites, item_nbonds, nexact, out, hist, true, geom, rows);
+}
+
+int perc_batch_clusters_geom_seeded(perc_ctx* h, int kind, int ntrials, const int* site_seeds,
+                                    const int* bond_seeds, int nitems, const int* item_trial,
+                                    const int* item_nsites, const int* item_nbonds, int nexact,
+                                    perc_cluster_item* out, int* hist, perc_cluster_geom* geom, long long* rows) {
+  return batch_clusters_impl("perc_batch_clusters_geom_seeded", true, h, kind, ntrials, site_seeds, bond_seeds,
+                             nitems, item_trial, item_nsites, item_nbonds, nexact, out, hist, true, geom, rows);
 }
 
 }  // extern "C"

@@ -516,8 +516,8 @@ int perc_set_dot_order(perc_ctx *h, int order);
 /* What the last solve of the context actually ran: out4[0] = kernel family
    (0 other launched kernels: LDS tiles, split stencil, CSR; PERC_RAN_MARCH,
    PERC_RAN_RESIDENT, PERC_RAN_SMALL), out4[1] = PERC_RAN_* flag bits,
-   out4[2] = iterations, out4[3] = 0 (reserved).  PERC_ESTATE before any
-   solve. */
+   out4[2] = iterations, out4[3] = iterations in which the march skipped dead
+   bands (PERC_RAN_FRONT).  PERC_ESTATE before any solve. */
 #define PERC_RAN_MARCH 1
 #define PERC_RAN_SLABS 2      /* row slabs (perc_set_slabs) */
 #define PERC_RAN_RESIDENT 3
@@ -532,6 +532,10 @@ int perc_set_dot_order(perc_ctx *h, int order);
 #define PERC_RAN_XCD_GROUPED 128 /* resident solve: XCD-grouped reductions (else the flat all-gather) */
 /* (bit 256 of out4[1] is retired -- it marked the deferred reductions -- and is not to be reused) */
 #define PERC_RAN_OPEN 512     /* strip-major nibble march: the open-lattice kernels (open-square path alone) */
+/* the march skipped the bands the Krylov front had not reached (x0 = 0, one
+   slab, the launched q-free march; PERC_MARCH_FRONT=0 in the environment
+   turns it off); out4[3] counts the iterations that ran with such a band */
+#define PERC_RAN_FRONT 1024
 int perc_last_solve(perc_ctx *h, int *out4);
 /* err of every iteration of the last solve (linbcg's per-iteration
    `write (*,*) iter, err`, bondc.f:834): min(cap, iterations) values into
@@ -1163,6 +1167,8 @@ int perc_nr_status_(void);  /* F77 spelling: `integer perc_nr_status` */
    NR drop-in reproduces the reference solver bitwise; PERC_DOT_FAST: the
    wave-tree sums of perc_conductance) */
 int perc_nr_set_dot_order(int order);
+/* perc_last_solve of linbcg_'s own context (PERC_ESTATE before its first solve) */
+int perc_nr_last_solve(int *out4);
 /* call nearestn(rn) (Square/bondc.f:617-715, Triangular/bondc.f:619-804):
    the neighbours of site rn into the caller's blank COMMON m, n, t, pbc,
    nn(10), scn (symbol __BLNK__; scn 4 square, 6 triangular), zeros where a

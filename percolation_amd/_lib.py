@@ -35,6 +35,7 @@ RAN_OTHER, RAN_MARCH, RAN_SLABS, RAN_RESIDENT, RAN_SMALL = 0, 1, 2, 3, 4
 RAN_LITERAL, RAN_LIT_TERMS, RAN_QFREE, RAN_STRIPS, RAN_NIBBLE, RAN_TAG, RAN_HOST_FOLD = 1, 2, 4, 8, 16, 32, 64
 RAN_XCD_GROUPED = 128
 RAN_OPEN = 512  # (256 is retired: perc.h)
+RAN_FRONT = 1024
 XPORT_RCCL, XPORT_HOST, XPORT_EXCHANGE = 0, 1, 4
 DSLAB_ID_BYTES = 128
 
@@ -210,6 +211,7 @@ SIGNATURES = {
     "perc_nr_status": (C.c_int, []),
     "perc_nr_status_": (C.c_int, []),
     "perc_nr_set_dot_order": (C.c_int, [C.c_int]),
+    "perc_nr_last_solve": (C.c_int, [_VP]),
     "perc_shuffle_seeded": (None, [C.c_int, C.c_int, _I]),
     "perc_ensemble_create": (C.c_int, [C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]),

@@ -599,7 +599,9 @@ class Context:
         family ('other', 'march', 'slabs', 'resident', 'small'), its flags and
         the iteration count.  lit_terms: the literal folds summed the terms
         the solve kernels themselves stored (the production kernels ran).
-        open: the strip-major nibble march ran its open-lattice kernels."""
+        open: the strip-major nibble march ran its open-lattice kernels.
+        front / front_iters: the march skipped the bands the Krylov front had
+        not reached, in that many iterations."""
         out = np.zeros(4, dtype=np.int32)
         L.check(L.lib().perc_last_solve(self.h, out.ctypes.data), "perc_last_solve")
         f = int(out[1])
@@ -608,7 +610,8 @@ class Context:
                     qfree=bool(f & L.RAN_QFREE), strips=bool(f & L.RAN_STRIPS),
                     nibble=bool(f & L.RAN_NIBBLE), tag=bool(f & L.RAN_TAG),
                     host_fold=bool(f & L.RAN_HOST_FOLD), xcd_grouped=bool(f & L.RAN_XCD_GROUPED),
-                    open=bool(f & L.RAN_OPEN), iter=int(out[2]))
+                    open=bool(f & L.RAN_OPEN), front=bool(f & L.RAN_FRONT), front_iters=int(out[3]),
+                    iter=int(out[2]))
 
     def matrix_format(self):
         rc = L.lib().perc_matrix_format(self.h)

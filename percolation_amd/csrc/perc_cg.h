@@ -102,7 +102,12 @@ struct CGArgs {
   // Set (non-null) only for the kernels' LIT instantiation -- the same
   // source with those stores compiled in; nullptr in the fast order
   double* lit;
+  // the march's live rows [flo, fhi): a band that misses them is skipped
+  // (k_cg_march `active`).  Every row (kFrontAllLo / Hi) unless dev_solve
+  // knows how far the Krylov front has come (MarchFront, perc_solve.hip)
+  int flo, fhi;
 };
+constexpr int kFrontAllLo = -(1 << 30), kFrontAllHi = 1 << 30;
 
 // diagonal of rows i, i+1 (i even) from the CSR diag array or the stencil code
 template <bool ST>
@@ -949,6 +954,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_init(CGArgs a, int itol, int x0_z
   int i0, i1;
   block_rows(N, &i0, &i1);
   double acc[2] = {0.0, 0.0};  // bnrm^2, z.r
+  int ilo = INT_MAX, ihi = -1;  // the nonzero r0 of this thread's rows (CGScalars::rlo, rhi)
   for (int i = i0 + threadIdx.x; i < i1; i += kBlock) {
     const double di = diag1<ST>(a, i);
     double ax = 0.0;
@@ -963,10 +969,24 @@ __global__ __launch_bounds__(kBlock) void k_cg_init(CGArgs a, int itol, int x0_z
     }
     const double ri = b[i] - ax;
     a.r[i] = ri;
+    if (ri != 0.0) {
+      ilo = min(ilo, i);
+      ihi = max(ihi, i);
+    }
     const double zb = itol == 1 ? b[i] : b[i] / di;
     acc[0] = acc[0] + zb * zb;
     const double zr = ri / di;
     acc[1] = acc[1] + zr * ri;
+  }
+  // one atomic pair per wave that saw a nonzero (the lattice solves: the
+  // waves of one row)
+  for (int o = 32; o > 0; o >>= 1) {
+    ilo = min(ilo, __shfl_xor(ilo, o));
+    ihi = max(ihi, __shfl_xor(ihi, o));
+  }
+  if ((threadIdx.x & 63) == 0 && ihi >= 0) {
+    atomicMin(&a.S->rlo, ilo);
+    atomicMax(&a.S->rhi, ihi);
   }
   double tot[2];
   if (publish_and_reduce<2>(acc, a.partials + 2 * a.pstride, a.tickets + 2 * a.tstride, lb,
@@ -1107,6 +1127,8 @@ CGArgs make_cg_args(perc_ctx* h) {
   a.ez = nullptr;
   a.mes = 0;
   a.lit = nullptr;
+  a.flo = kFrontAllLo;
+  a.fhi = kFrontAllHi;
   return a;
 }
 

@@ -1096,7 +1096,7 @@ int perc_last_solve(perc_ctx* h, int* out4) {
   out4[0] = h->last_kernel;
   out4[1] = h->last_flags;
   out4[2] = h->last_iter;
-  out4[3] = 0;
+  out4[3] = h->last_front;
   return PERC_OK;
 }
 

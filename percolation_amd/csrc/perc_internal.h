@@ -68,6 +68,10 @@ struct CGScalars {
   // ak of the previous iteration (the march P's collector keeps it when it
   // forms the new ak): B(k + 1) applies x += ak(k) p(k) at its start (CGArgs::mxin)
   double akprev;
+  // lowest and highest index i (row-major) of a nonzero r0 (k_cg_init's
+  // integer atomic min / max; the host starts them at INT_MAX and -1): the
+  // source rows of the march's Krylov front (MarchFront, perc_solve.hip)
+  int rlo, rhi;
 };
 
 struct AsmParams {
@@ -168,6 +172,7 @@ struct MarchKnobs {
   bool edge_step = false;  // PERC_MARCH_EDGE_STEP: B stores its edge pairs per step, not staged in LDS
   bool xafter = false;     // PERC_MARCH_XAFTER: x updated after each B's walk, not at the next B's start
   bool res_flat = false;   // PERC_RES_FLAT: the resident solve's flat all-gather reductions
+  bool front = true;       // PERC_MARCH_FRONT=0: every band walks in every iteration (no Krylov-front skip)
   int time_every = 64;     // PERC_TIME_EVERY=<n>: kernel timing samples every n-th iteration of a
                            // chunk (read once per process)
   const char* trace = nullptr;  // PERC_MARCH_TRACE=<csv>: phase probe of the strip-major march
@@ -254,6 +259,7 @@ struct perc_ctx {
   // and flags (PERC_RAN_* bits: q-free, strip-major, nibble codes, tagged
   // reductions, literal folds of kernel-stored terms)
   int last_kernel = 0, last_flags = 0, last_iter = -1;
+  int last_front = 0;           // ... and how many of its iterations skipped dead bands (PERC_RAN_FRONT)
   bool full_voltages = false;   // perc_set_full_voltages: keep x on every row
   int nslab = 1;                // perc_set_slabs: row slabs of the CG solve
   perc::DSlab* dslab = nullptr;  // perc_dslab_*: this process's slab of a distributed solve

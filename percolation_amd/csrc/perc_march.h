@@ -924,7 +924,13 @@ __global__ __launch_bounds__(64 * kMarchWaves, march_min_waves(MODE, SM, PK)) vo
   }
   g.r0 = rows.r0;
   g.rend = rows.rend;
-  const bool active = g.r0 < nrows;  // wave-uniform
+  // wave-uniform.  A band that misses the launch's live rows [a.flo, a.fhi)
+  // (CGArgs::flo: the rows the Krylov front has reached, from the host) is
+  // dead: every value it would load, form or store is an exact zero, so it
+  // does none of it -- no ring loads, no p / r / edge-pair / term stores, no
+  // x update -- and its +0.0 partials enter the reduction below exactly where
+  // they always do (same grid, same granules, same association)
+  const bool active = g.r0 < nrows && g.r0 < a.fhi && g.rend > a.flo;
   const int c0 = strip * kMarchW;
   g.col = c0 + 2 * lane;
   g.hcol = lane == 0 ? c0 - 1 : c0 + kMarchW;

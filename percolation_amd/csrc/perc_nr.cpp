@@ -202,6 +202,10 @@ int perc_nr_set_dot_order(int order) {
   g_nr_dot = order;
   return PERC_OK;
 }
+int perc_nr_last_solve(int* out4) {
+  std::lock_guard<std::mutex> lk(g_nr_mu);
+  return g_nr ? perc_last_solve(g_nr, out4) : PERC_ESTATE;
+}
 // the same for F77 callers (implicit interface: integer perc_nr_status)
 int perc_nr_status_(void) { return g_status; }
 

@@ -762,6 +762,7 @@ MarchKnobs read_march_knobs() {
   k.edge_step = flag("PERC_MARCH_EDGE_STEP");
   k.xafter = flag("PERC_MARCH_XAFTER");
   k.res_flat = flag("PERC_RES_FLAT");
+  if (const char* v = std::getenv("PERC_MARCH_FRONT")) k.front = v[0] != '0';
   if (time_every > 0) k.time_every = time_every;  // (else the default)
   k.trace = std::getenv("PERC_MARCH_TRACE");
   k.trace_it = num("PERC_MARCH_TRACE_IT", 1000);
@@ -794,7 +795,7 @@ hipError_t prepare_march(perc_ctx* h, CGArgs& a, int itmax, bool probe) {
 hipError_t dev_solve(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,
                      int* iter, double* err) {
   h->knobs = read_march_knobs();
-  h->last_kernel = h->last_flags = 0;
+  h->last_kernel = h->last_flags = h->last_front = 0;
   h->last_iter = -1;
   const hipError_t e = dev_solve_impl(h, itol, tol, itmax, x0_zero, full_x, iter, err);
   if (e == hipSuccess) h->last_iter = *iter;
@@ -1108,6 +1109,88 @@ hipError_t dev_solve_x34(perc_ctx* h, int itol, double tol, int itmax, int* iter
   return hipSuccess;
 }
 
+// The Krylov front of a launched march solve that starts from x0 = 0.
+//
+// r(0) = b is nonzero on the lattice rows [lo, hi] only (the driven row next
+// to the Va electrode; k_cg_init records them, CGScalars::rlo / rhi).  The
+// Jacobi preconditioner is diagonal and the operator couples a row to rows
+// within `reach` = 1 of it (the forms table's row offsets), so by induction
+// over linbcg's recurrences
+//   p(1) = z(0)                 is nonzero within 0 rows of [lo, hi],
+//   q(k) = A p(k), r(k) = r(k-1) - ak q(k)   within one row more than p(k),
+//   p(k+1) = bk p(k) + r(k) / d              within as many rows as r(k):
+// p(k) reaches k - 1 rows, q(k), r(k), z(k) and B's edge pairs k rows, and
+// the x update B(k) applies (ak(k-1) p(k-1)) k - 2 rows.  Every other row of
+// them is an exact zero, and so are its terms of q.p, z.r and r.r: a band
+// that misses [lo - k, hi + k] loads zeros, forms zeros and stores zeros in
+// launch k, and what it would store is already there -- the first chunk's
+// launches walk every band, so both p buffers, r, the edge pairs and the
+// literal order's term buffer hold the parent's own zeros on every row the
+// front has not reached, and no kernel of the solve writes them again before
+// the front arrives.  (Zeros added to x, a partial or a literal fold leave it
+// bitwise what it was; a skipped band's own partial is +0.0 either way.)
+//
+// Launch k gets [lo - (k + 1), hi + (k + 1)], one row more than the bound.
+// The row is deliberate: k is the host's count of launches, the device's
+// iteration is S->iter + 1, and the two agree only while the solve runs; a
+// bound that is tight to the row would turn any slip of one between them (a
+// launch re-ordered in a later change, p's reach counted from 1) into wrong
+// numbers, where the margin costs one band one iteration early.
+//
+// On only when x0 = 0, one slab, the launched q-free march, the operator's
+// row reach 1 and no phase trace; PERC_MARCH_FRONT=0 turns it off.
+struct MarchFront {
+  bool on = false;     // the conditions hold
+  bool known = false;  // rows [lo, hi] read back and some band still dead
+  int lo = 0, hi = -1;
+  int last_dead = 0;   // the last iteration launched with a dead band
+};
+
+int forms_row_reach(const StencilForms& F) {
+  int reach = 0;
+  for (int f = 0; f < F.nforms; ++f)
+    for (int j = 0; j < F.cnt[f]; ++j) reach = std::max(reach, std::abs(F.dr[f][j]));
+  return reach;
+}
+
+bool front_allowed(const perc_ctx* h, const CGArgs& a, bool x0_zero) {
+  return x0_zero && h->knobs.front && !h->knobs.trace && h->nslab <= 1 && !a.slab && h->stencil && h->march &&
+         h->qfree && a.T.m > 0 && a.T.nrows > 0 && (long long)a.T.m * a.T.nrows == h->N &&
+         forms_row_reach(h->forms) == 1;
+}
+
+// does some band of the march P (which = 0) or B (1) miss a's live rows?  (the
+// bands as k_cg_march forms them, perc_bands.h)
+bool front_dead_band(const perc_ctx* h, const CGArgs& a, int which) {
+  const int nrows = a.T.nrows;
+  auto dead = [&](const BandRows& b) { return b.r0 < b.rend && !(b.r0 < a.fhi && b.rend > a.flo); };
+  if (a.wslots > 0) {
+    const int ns = a.wslots, Q = h->wm_grid / ns * kMarchWaves / (a.T.m / kMarchW);
+    for (int q = 0; q < Q; ++q)
+      for (int sl = 0; sl < ns; ++sl)
+        if (dead(slot_band(nrows, Q, q, ns, sl, a.wcum[which]))) return true;
+    return false;
+  }
+  for (int band = 0; band * a.T.bh < nrows; ++band)
+    if (dead(static_band(nrows, a.T.bh, band))) return true;
+  return false;
+}
+
+// the live rows of launch a.kiter
+void front_rows(const perc_ctx* h, MarchFront& F, CGArgs& a) {
+  a.flo = kFrontAllLo;
+  a.fhi = kFrontAllHi;
+  if (!F.known) return;
+  const int k = a.kiter, lo = F.lo - (k + 1), hi = F.hi + (k + 1);
+  if (lo <= 0 && hi >= a.T.nrows - 1) {  // the front has crossed the lattice
+    F.known = false;
+    return;
+  }
+  a.flo = std::max(lo, 0);
+  a.fhi = std::min(hi + 1, a.T.nrows);
+  if (front_dead_band(h, a, 0) || front_dead_band(h, a, 1)) F.last_dead = k;
+}
+
 hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,
                           int* iter, double* err) {
   DeviceBuffers& d = h->d;
@@ -1127,6 +1210,8 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
   hs.tol = tol;
   hs.itmax = itmax;
   hs.bkden = 1.0;
+  hs.rlo = INT_MAX;  // (k_cg_init's atomic min / max)
+  hs.rhi = -1;
   HIP_TRY(hipMemcpyAsync(d.scal, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(d.tickets, 0, kRedSlots * red_tickets_size(red_grid(h)) * sizeof(unsigned),
                          st));
@@ -1198,11 +1283,15 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
   }
   if (!(h->march && h->qfree)) a.lit = nullptr;  // (the other kernels store no terms)
   HIP_TRY(prepare_march(h, a, itmax, false));
+  MarchFront front;
+  front.on = front_allowed(h, a, x0_zero);
+  if (front.on) h->last_flags |= PERC_RAN_FRONT;
   HostFold hf;
   const bool host_fold = (h->last_flags & PERC_RAN_HOST_FOLD) != 0;
   if (host_fold) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hf.t), sizeof(double) * 3 * (size_t)h->N));
   // iterate in chunks; the device flag makes surplus launches no-ops
-  int chunk = 8;
+  constexpr int kFirstChunk = 8;
+  int chunk = kFirstChunk;
   CGScalars* hsp = nullptr;
   HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hsp), sizeof(CGScalars)));
   hipError_t e = hipSuccess;
@@ -1239,6 +1328,7 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
       const bool tm = T.enabled && j % kTimeEvery == 0;
       hipEvent_t* ev = tm ? &T.ev[kEv * j] : nullptr;
       a.kiter = (int)(launched + j + 1);
+      front_rows(h, front, a);
       // (tag: exact in a double while solve_epoch < 2^29)
       a.mtag = (double)(((unsigned long long)h->solve_epoch << 24) | (unsigned long long)a.kiter);
       const int mti = a.kiter - mt_it;
@@ -1297,6 +1387,12 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
     }
     done_iters = hsp->iter;
     if (hsp->done) break;
+    // the first chunk walked every band; its read-back brings the source rows
+    if (front.on && launched == kFirstChunk && hsp->rhi >= hsp->rlo) {
+      front.lo = hsp->rlo / a.T.m;
+      front.hi = hsp->rhi / a.T.m;
+      front.known = front.hi < a.T.nrows;
+    }
     if (launched > (long long)itmax + 2) break;  // cannot happen: device stops at itmax+1
     chunk = std::min(chunk * 2, kMaxChunk);
   }
@@ -1334,6 +1430,8 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
   }
   *iter = hsp->iter;
   *err = hsp->err;
+  // iterations that ran with a dead band (the launches past the stop did nothing)
+  h->last_front = std::max(0, std::min(hsp->iter, front.last_dead) - kFirstChunk);
   hipHostFree(hsp);
   return e;
 }

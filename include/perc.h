@@ -483,10 +483,12 @@ int perc_set_march_rows(perc_ctx *h, int rows);
    PERC_MARCH_TAG | PERC_MARCH_NIBBLE)
 int perc_set_march_mode(perc_ctx *h, int mode);
 /* Per-round band weights of the slot-weighted bands (PERC_MARCH_SLOTS):
-   which = 0 the strip-major P kernel, 1 its B kernel, 2 the row-major P past
-   the Infinity Cache; n = 0 restores every default (100:75:50, 100:80:60,
-   flat).  A tuning / test knob: the rows stay a partition of the lattice
-   whatever the weights. */
+   which = 0 the strip-major P kernel, 1 its B kernel; n = 0 restores both
+   defaults (100:76:48:40, 100:78:55:50).  which = 2 was the row-major P past
+   the Infinity Cache, which runs on B's 8-row bands since round 4: it is
+   still accepted (valid weights return PERC_OK) and changes nothing.  A
+   tuning / test knob: the rows stay a partition of the lattice whatever the
+   weights. */
 int perc_set_band_weights(perc_ctx *h, int which, int n, const int *w);
 
 /* Association of linbcg's three dot products (Square/bondc.f:785-787 bknum,

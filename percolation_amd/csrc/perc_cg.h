@@ -30,8 +30,6 @@ struct TileGeom {
   int bh;                  // band height of the register-march kernel
 };
 
-constexpr int kMaxSlotRounds = 4;
-
 struct CGArgs {
   CsrView A;
   StencilView St;
@@ -758,7 +756,8 @@ __global__ __launch_bounds__(64) void k_fold_b(CGArgs a) {
 // launched kernels' (p = bk p + r/d, q, r -= ak q, x += ak p); the dots are
 // summed per thread in row order, then wave butterflies, then the waves in
 // order.  The prologue (r, bnrm, the first bknum) is k_cg_init's.
-constexpr int kSmallThreads = 1024, kSmallEPT = 8, kSmallRows = kSmallThreads * kSmallEPT;
+constexpr int kSmallThreads = 1024, kSmallEPT = 8;
+static_assert(kSmallRows == kSmallThreads * kSmallEPT, "kSmallRows (perc_solve_plan.h)");
 
 // ST: the stencil operator (row codes in registers, the forms' offsets in
 // LDS: no global memory access in the loop but the x update); else the CSR
@@ -1059,10 +1058,6 @@ __global__ __launch_bounds__(kBlock) void k_pack_nib(TileGeom T, const uint16_t*
 }
 
 
-// a vector larger than this does not stay in the 256 MB Infinity Cache
-// between kernels (L = 8192: 537 MB; L = 4096: 134 MB)
-constexpr size_t kLargeVector = (size_t)256 << 20;
-
 // workgroups of the largest reduction (CG kernels or the tiled kernel)
 int red_grid(const perc_ctx* h) { return std::max({h->grid, h->tile_grid, h->march_grid_max, h->row_grid}); }
 
@@ -1085,15 +1080,15 @@ CGArgs make_cg_args(perc_ctx* h) {
   a.T = TileGeom{h->g.m, h->g.n - 2, h->g.pbc, (h->g.m + kTileW - 1) / kTileW, h->march_h};
   a.pb[0] = h->d.p0;
   a.pb[1] = h->d.p1;
-  a.fused = h->fused ? 1 : 0;
+  a.fused = h->plan.fused ? 1 : 0;
   // fused format: B walks its row chunks in reverse, so it starts on the q
   // the tiled kernel wrote last (still in the 256 MB Infinity Cache), and
   // the next tiled kernel starts on the r that B wrote last (measured: B
   // 0.112 -> 0.097 ms at L = 4096)
-  a.b_reverse = h->fused ? 1 : 0;
+  a.b_reverse = h->plan.fused ? 1 : 0;
   a.kiter = 1;
-  a.march_alt = h->march_alt ? 1 : 0;
-  a.bx = h->march && !h->qfree ? 1 : 0;
+  a.march_alt = h->plan.march_alt ? 1 : 0;
+  a.bx = h->plan.march && !h->plan.qfree ? 1 : 0;
   a.sm = 0;  // dev_solve / dev_bench switch to the strip-major copies
   a.glo = 0;
   a.ghi = h->g.n - 2;

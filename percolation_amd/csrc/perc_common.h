@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_apply(const int* in, int 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 constexpr unsigned kOOB = 0x80000000u;  // buffers are kept below 2 GB (march_geometry)
-constexpr int kNT = 2;                  // aux bits: nontemporal
+// (kNT, the nontemporal aux bits: perc_solve_plan.h)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
 }
@@ -395,6 +395,52 @@ template <typename T>
 hipError_t dmalloc(T** p, size_t n) {
   return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (n ? n : 1));
 }
+
+// Scratch memory a function owns for one call: device (DevBuf) or pinned host
+// (PinnedBuf) memory, freed when the owner goes out of scope -- on every early
+// return too.  Move-only; get() is null until alloc succeeds.
+template <typename T, hipError_t (*Free)(void*)>
+class OwnedBuf {
+ public:
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf&) = delete;
+  OwnedBuf& operator=(const OwnedBuf&) = delete;
+  OwnedBuf(OwnedBuf&& o) noexcept : p_(o.release()) {}
+  OwnedBuf& operator=(OwnedBuf&& o) noexcept {
+    if (this != &o) reset(o.release());
+    return *this;
+  }
+  ~OwnedBuf() { reset(); }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  T* operator->() const { return p_; }
+  T* release() {
+    T* p = p_;
+    p_ = nullptr;
+    return p;
+  }
+  void reset(T* p = nullptr) {
+    if (p_) (void)Free(p_);
+    p_ = p;
+  }
+
+ protected:
+  T* p_ = nullptr;
+};
+template <typename T>
+struct DevBuf : OwnedBuf<T, hipFree> {
+  hipError_t alloc(size_t n) {  // n elements (the previous block is freed first)
+    this->reset();
+    return dmalloc(&this->p_, n);
+  }
+};
+template <typename T>
+struct PinnedBuf : OwnedBuf<T, hipHostFree> {
+  hipError_t alloc(size_t n) {
+    this->reset();
+    return hipHostMalloc(reinterpret_cast<void**>(&this->p_), sizeof(T) * (n ? n : 1));
+  }
+};
 
 // *p grown to n elements (capacity *cap); the contents are not kept
 template <typename T>

@@ -981,12 +981,9 @@ int perc_set_band_weights(perc_ctx* h, int which, int n, const int* w) {
     if (w[i] <= 0) return PERC_EINVAL;
   if (n == 0) {
     h->slot_w_set = false;
-  } else {
-    if (!h->slot_w_set) {  // start from the defaults
-      const int def[3][4] = {{100, 76, 48, 40}, {100, 78, 55, 50}, {100, 100, 100, 100}};  // (kSlotW)
-      std::memcpy(h->slot_w, def, sizeof(def));
-    }
-    for (int i = 0; i < 4; ++i) h->slot_w[which][i] = i < n ? w[i] : h->slot_w[which][i];
+  } else if (which < 2) {  // (2, the row-major P's set: no kernel has read it since round 4)
+    if (!h->slot_w_set) std::memcpy(h->slot_w, kSlotW, sizeof(kSlotW));  // start from the defaults
+    for (int i = 0; i < n; ++i) h->slot_w[which][i] = w[i];
     h->slot_w_set = true;
   }
   march_geometry(h);
@@ -1081,12 +1078,12 @@ int perc_set_conductcalc_weights(perc_ctx* h, int rule, unsigned int seed) {
 int perc_march_info(perc_ctx* h, int* out5) {
   if (!h || !out5) return PERC_EINVAL;
   if (!h->assembled) return PERC_ESTATE;
-  out5[0] = h->small ? 4 : (h->resident && h->stencil ? 3 : (h->march ? 1 : 0));
-  out5[1] = (h->qfree ? 1 : 0) | (h->strips ? 2 : 0) | (h->march_slots ? 8 : 0) |
-            (h->march_tag ? 16 : 0) | (h->nib_used && out5[0] == 1 ? 32 : 0);
-  out5[2] = h->march_alt ? 1 : 0;
-  out5[3] = h->resident ? h->res_H : (h->march ? h->march_h : 0);
-  out5[4] = h->resident ? h->g.m : (h->march ? 128 : 0);
+  out5[0] = h->plan.family();  // (PERC_RAN_MARCH 1, PERC_RAN_RESIDENT 3, PERC_RAN_SMALL 4)
+  out5[1] = (h->plan.qfree ? 1 : 0) | (h->plan.strips ? 2 : 0) | (h->plan.march_slots ? 8 : 0) |
+            (h->plan.march_tag ? 16 : 0) | (h->nib_used && out5[0] == 1 ? 32 : 0);
+  out5[2] = h->plan.march_alt ? 1 : 0;
+  out5[3] = h->plan.resident ? h->res_H : (h->plan.march ? h->march_h : 0);
+  out5[4] = h->plan.resident ? h->g.m : (h->plan.march ? 128 : 0);
   return PERC_OK;
 }
 
@@ -1103,9 +1100,9 @@ int perc_last_solve(perc_ctx* h, int* out4) {
 int perc_matrix_format(perc_ctx* h) {
   if (!h) return PERC_EINVAL;
   if (!h->assembled) return PERC_ESTATE;
-  if (!h->stencil) return PERC_FMT_CSR;
-  if (!h->fused) return PERC_FMT_STENCIL_SPLIT;
-  return h->march ? PERC_FMT_STENCIL : PERC_FMT_STENCIL_TILED;
+  if (!h->plan.stencil) return PERC_FMT_CSR;
+  if (!h->plan.fused) return PERC_FMT_STENCIL_SPLIT;
+  return h->plan.march ? PERC_FMT_STENCIL : PERC_FMT_STENCIL_TILED;
 }
 
 int perc_selftest_division(long long n, unsigned long long seed, unsigned long long* out3) {

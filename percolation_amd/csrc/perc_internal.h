@@ -9,6 +9,7 @@
 
 #include "../../include/perc.h"
 #include "lattice.h"
+#include "perc_solve_plan.h"
 
 namespace perc {
 
@@ -219,23 +220,19 @@ struct perc_ctx {
   int perccln = 0;
   int rule = -1;
   int fmt_req = PERC_FMT_AUTO;  // perc_set_matrix_format
+  perc::SolvePlan plan;         // what a solve runs (select_format; the rules: perc_solve_plan.h)
   bool stencil_ok = false;      // every stencil slot of the assembled system has a bond
-  bool stencil = false;         // solver kernels use the stencil operator
   bool tiled_ok = false;        // every row's slots are (row, col) +-1 steps of its form
-  bool fused = false;           // stencil P+S fused into the LDS-tiled kernel
   int tile_grid = 0;            // workgroups of the tiled kernel
   int tile_h = 32;              // its tile height (rows)
   bool march_ok = false;        // register-march kernel usable (m % 128 == 0, tileable)
-  bool march = false;           // fused format runs the register-march kernel
   int march_h = 32;             // its band height (rows per wave)
-  int march_slots = 0;          // q-free strip-major march: slot-weighted bands
-  int march_tag = 0;            // q-free strip-major march: tagged-granule reductions
   unsigned solve_epoch = 0;     // tags of the granule reductions
   int wm_slots = 0;             // slot-weighted bands: workgroup rounds (0: not available)
   int wm_grid = 0;              // their grid (CUs x rounds)
-  int wm_cum[3][5] = {};        // cumulative round weights (P, B, row-major P)
+  int wm_cum[2][perc::kMaxSlotRounds + 1] = {};  // cumulative round weights (P, B)
   bool slot_w_set = false;      // perc_set_band_weights: weights instead of the defaults
-  int slot_w[3][4] = {};        // per round (P, B, row-major P)
+  int slot_w[2][perc::kMaxSlotRounds] = {};      // per round (P, B)
   int dot_order = PERC_DOT_FAST;  // perc_set_dot_order
   bool nib_ok = false;          // square-lattice column classes known (nibble codes)
   bool nib_used = false;        // the last strip-major solve ran the nibble codes
@@ -245,14 +242,9 @@ struct perc_ctx {
   int row_grid = 0;             // one CSR row per thread: cdiv(N, kBlock) (k_cg_spmv_row)
   int march_rows_req = 0;       // perc_set_march_rows (0: auto)
   int march_mode = PERC_MARCH_DEFAULT;  // perc_set_march_mode
-  bool qfree = false;           // march B rebuilds q (52N / iteration)
-  bool march_alt = false;       // alternating walk directions
-  bool strips = false;          // march solve in the strip-major layout
   int b_grid = 0;               // streaming B workgroups in the fused formats (dev_build_lattice)
   bool has_weights = false;     // perc_set_bond_weights: G = -g0 w for the spanning bonds
-  bool resident = false;        // persistent resident solve (k_cg_res)
-  bool small = false;           // one-workgroup solve of a small system (k_cg_small)
-  int res_G = 0, res_H = 0, res_MT = 0, res_HMAX = 0;  // its grid, band height, template
+  int res_G = 0, res_H = 0, res_MT = 0;  // the resident solve's grid, band height, template
   int res_NT = 1024;            // its threads per workgroup (m rounded up to 64 for m < 1024)
   bool res_uneven = false;      // a grouped resident launch found the XCD placement uneven
   // what the last dev_solve ran (perc_last_solve): kernel family (PERC_RAN_*)
@@ -294,7 +286,7 @@ hipError_t dev_canon(perc_ctx* h, int* canon_out);
 hipError_t dev_cluster_sizes(perc_ctx* h, int kind, int root, int* maxcs, int* rootsize);
 hipError_t dev_assemble(perc_ctx* h, int rule, double g0, double leak, double Va, int span_root);
 hipError_t ensure_csr(perc_ctx* h);  // the CSR copy of the assembled system, on demand
-void select_format(perc_ctx* h);  // stencil / fused flags from fmt_req + assembly checks
+void select_format(perc_ctx* h);  // h->plan from the requests + assembly checks (solve_plan)
 void march_geometry(perc_ctx* h); // band height + grid of the register-march kernel
 void res_geometry(perc_ctx* h);   // grid + band height of the resident solve
 // force_exchange: run the combines and publishes even at K = 1 (measures
@@ -307,10 +299,11 @@ void dslab_comm_release(perc_ctx* h);
 hipError_t dev_dslab_status(perc_ctx* h, int* iter, double* err, int* done);
 hipError_t dev_dslab_end(perc_ctx* h, bool to_ctx);
 hipError_t dev_x_row(perc_ctx* h, int row, double* buf, bool to_ctx);
-// row forms of the interior system (perc_assemble.hip); band height of the
-// register march over nrows rows (perc_solve.hip)
+// row forms of the interior system (perc_assemble.hip); CUs of the device and
+// the workgroups a CU holds of the kernel that sizes the march's bands
+// (perc_solve.hip; march_rows_for and slot_geometry take them)
 StencilForms stencil_forms(const Geom& g);
-int march_rows_for(const perc_ctx* h, int nrows);
+void march_occupancy(const perc_ctx* h, int* cus, int* per_cu);
 hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, bool full_x,
                            int* iter, double* err);
 hipError_t dev_solve(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,

@@ -391,8 +391,7 @@ __device__ __forceinline__ double march_q_map(unsigned c, double d, double xi, u
 // r2_14_march_depth5.log): waves per SIMD, not rows in flight, decide.  Before the memory instructions were
 // made unconditional (MBuf) every step waited for vmcnt(0) and deeper
 // prefetch could not help.  The opt-in variants (q-free P and B, strip-
-// major) keep D = 2.
-constexpr int kMarchDepth = 2;
+// major) keep D = 2 (kMarchDepth, perc_solve_plan.h).
 
 // Register march, three kernels of one loop (MODE):
 //   kMarchPQ: P(k)+S(k), stores q for the streaming B (k_cg_b)
@@ -405,7 +404,7 @@ constexpr int kMarchDepth = 2;
 // halo rows two neighbouring bands share are read by both waves at the
 // same moment (start or end of the walk: the second read hits L2 / the
 // Infinity Cache), and B starts each band on the rows P wrote last.
-constexpr int kMarchPQ = 0, kMarchP = 1, kMarchB = 2;
+// (kMarchPQ, kMarchP, kMarchB: perc_solve_plan.h)
 
 struct MGeom {
   int r0, rend, col, hcol;
@@ -1148,98 +1147,15 @@ __global__ __launch_bounds__(kBlock) void k_march_xpend(CGArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// The march variants: k_cg_march's template arguments as a value, and the
-// list of every instantiation libperc compiles -- the only place one is
-// named.  perc_solve.hip builds its lookup table from the list and picks a
-// key per launch (select_march); the row-slab solves launch the q-storing
-// entry alone (march_pq_kernel), so perc_slabs.hip compiles just that one.
-struct MarchKey {
-  int mode;  // kMarchPQ / kMarchP / kMarchB
-  bool sm;   // strip-major layout
-  int d, paux;
-  bool tr, tag, pk, lit;
-  int esr;
-  bool open;  // strip-major nibble codes on an open lattice: the open-square path alone
-};
+// The march variants: perc_solve_plan.h holds the list of every instantiation
+// libperc compiles, as keys (MarchKey, PERC_MARCH_VARIANTS); PERC_MARCH_ROW
+// pairs a row of it with its kernel.
 using MarchKernel = void (*)(CGArgs);
 struct MarchVariant {
   MarchKey key;
   MarchKernel fn;
 };
 #define PERC_MARCH_ROW(...) MarchVariant{MarchKey{__VA_ARGS__}, k_cg_march<__VA_ARGS__>},
-
-// q-storing P+S: row slabs, modes without QFREE, literal order past 2 GB of terms
-#define PERC_MARCH_PQ kMarchPQ, false, 3, 0, false, false, false, false, 0
-// tagged strip-major P on the u16 codes: the kernel whose occupancy sizes the
-// bands (march_rows_for, march_geometry)
-#define PERC_MARCH_OCC kMarchP, true, 3, kNT, false, true, false, false, 0
-
-// Strip-major rows (the default solve at L <= 4096): 3 rows prefetched,
-// nontemporal last-use loads.  Row-major rows (vectors past the Infinity
-// Cache): kMarchDepth rows, P and B on B's 8-row bands (L = 8192: P 0.314 vs
-// 0.355 ms, r4_8; B's nontemporal r(k) loads 0.300 vs 0.331 ms, r4_3).
-// Columns: MODE, SM, D, PAUX, TR, TAG, PK, LIT, ESR, OPEN (k_cg_march's
-// order; a row without the last column has OPEN false).  Every strip-major
-// nibble row has an OPEN twin: the twin runs on the open lattice, the row
-// itself under pbc (select_march).
-#define PERC_MARCH_VARIANTS(X) \
-  X(PERC_MARCH_PQ)                                                   /* q-storing P+S */ \
-  X(kMarchP, true, 3, kNT, false, false, false, false, 0)            /* strip-major P, u16, ticket reduction */ \
-  X(kMarchP, true, 3, kNT, true, false, false, false, 0)             /* strip-major P, u16, ticket reduction, phase probe */ \
-  X(PERC_MARCH_OCC)                                                  /* strip-major P, u16, tagged granules */ \
-  X(kMarchP, true, 3, kNT, true, true, false, false, 0)              /* strip-major P, u16, tagged granules, phase probe */ \
-  X(kMarchP, true, 3, kNT, false, false, false, true, 0)             /* strip-major P, u16, literal order */ \
-  X(kMarchP, true, 3, kNT, false, true, false, true, 0)              /* strip-major P, u16, literal order, solve tagged */ \
-  X(kMarchP, true, 3, kNT, false, false, true, false, 0)             /* strip-major P, nibble, ticket reduction */ \
-  X(kMarchP, true, 3, kNT, false, false, true, false, 0, true)       /* strip-major P, nibble, ticket reduction, open lattice */ \
-  X(kMarchP, true, 3, kNT, true, false, true, false, 0)              /* strip-major P, nibble, ticket reduction, phase probe */ \
-  X(kMarchP, true, 3, kNT, true, false, true, false, 0, true)        /* strip-major P, nibble, ticket reduction, phase probe, open lattice */ \
-  X(kMarchP, true, 3, kNT, false, true, true, false, 0)              /* strip-major P, nibble, tagged granules (pbc) */ \
-  X(kMarchP, true, 3, kNT, false, true, true, false, 0, true)        /* strip-major P, nibble, tagged granules, open lattice: the default P */ \
-  X(kMarchP, true, 3, kNT, true, true, true, false, 0)               /* strip-major P, nibble, tagged granules, phase probe */ \
-  X(kMarchP, true, 3, kNT, true, true, true, false, 0, true)         /* strip-major P, nibble, tagged granules, phase probe, open lattice */ \
-  X(kMarchP, true, 3, kNT, false, false, true, true, 0)              /* strip-major P, nibble, literal order */ \
-  X(kMarchP, true, 3, kNT, false, false, true, true, 0, true)        /* strip-major P, nibble, literal order, open lattice */ \
-  X(kMarchP, true, 3, kNT, false, true, true, true, 0)               /* strip-major P, nibble, literal order, solve tagged */ \
-  X(kMarchP, true, 3, kNT, false, true, true, true, 0, true)         /* strip-major P, nibble, literal order, solve tagged, open lattice */ \
-  X(kMarchB, true, 3, kNT, false, false, false, false, 0)            /* strip-major B, u16, ticket reduction */ \
-  X(kMarchB, true, 3, kNT, true, false, false, false, 0)             /* strip-major B, u16, ticket reduction, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, true, false, false, 0)             /* strip-major B, u16, tagged granules */ \
-  X(kMarchB, true, 3, kNT, true, true, false, false, 0)              /* strip-major B, u16, tagged granules, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, false, false, true, 0)             /* strip-major B, u16, literal order */ \
-  X(kMarchB, true, 3, kNT, false, true, false, true, 0)              /* strip-major B, u16, literal order, solve tagged */ \
-  X(kMarchB, true, 3, kNT, false, true, false, false, kEdgeRows)     /* strip-major B, u16, edge pairs staged in LDS */ \
-  X(kMarchB, true, 3, kNT, true, true, false, false, kEdgeRows)      /* strip-major B, u16, staged edge pairs, phase probe */ \
-  X(kMarchB, true, 3, kNT, false, false, true, false, 0)             /* strip-major B, nibble, ticket reduction */ \
-  X(kMarchB, true, 3, kNT, false, false, true, false, 0, true)       /* strip-major B, nibble, ticket reduction, open lattice */ \
-  X(kMarchB, true, 3, kNT, true, false, true, false, 0)              /* strip-major B, nibble, ticket reduction, phase probe */ \
-  X(kMarchB, true, 3, kNT, true, false, true, false, 0, true)        /* strip-major B, nibble, ticket reduction, phase probe, open lattice */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, 0)              /* strip-major B, nibble, tagged granules */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, 0, true)        /* strip-major B, nibble, tagged granules, open lattice */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, 0)               /* strip-major B, nibble, tagged granules, phase probe */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, 0, true)         /* strip-major B, nibble, tagged granules, phase probe, open lattice */ \
-  X(kMarchB, true, 3, kNT, false, false, true, true, 0)              /* strip-major B, nibble, literal order */ \
-  X(kMarchB, true, 3, kNT, false, false, true, true, 0, true)        /* strip-major B, nibble, literal order, open lattice */ \
-  X(kMarchB, true, 3, kNT, false, true, true, true, 0)               /* strip-major B, nibble, literal order, solve tagged */ \
-  X(kMarchB, true, 3, kNT, false, true, true, true, 0, true)         /* strip-major B, nibble, literal order, solve tagged, open lattice */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, kEdgeRows)      /* strip-major B, nibble, edge pairs staged in LDS (pbc) */ \
-  X(kMarchB, true, 3, kNT, false, true, true, false, kEdgeRows, true) /* strip-major B, nibble, edge pairs staged in LDS, open lattice: the default B */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, kEdgeRows)       /* strip-major B, nibble, staged edge pairs, phase probe */ \
-  X(kMarchB, true, 3, kNT, true, true, true, false, kEdgeRows, true) /* strip-major B, nibble, staged edge pairs, phase probe, open lattice */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, false, false, 0)   /* row-major P, u16 */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, false, true, 0)    /* row-major P, u16, literal order */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, true, false, 0)    /* row-major P, nibble (128 VGPRs unspilled at the 4-wave bound): past the cache */ \
-  X(kMarchP, false, kMarchDepth, 0, false, false, true, true, 0)     /* row-major P, nibble, literal order */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, false, false, 0) /* row-major B, u16 */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, false, true, 0)  /* row-major B, u16, literal order */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, 0)  /* row-major B, nibble, edge pairs stored per step */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, true, true, 0)   /* row-major B, nibble, literal order */ \
-  X(kMarchB, false, kMarchDepth, kNT, false, false, true, false, kEdgeRowsRm) /* row-major B, nibble, edge pairs staged in LDS: past the cache */
-
-constexpr bool operator==(const MarchKey& a, const MarchKey& b) {
-  return a.mode == b.mode && a.sm == b.sm && a.d == b.d && a.paux == b.paux && a.tr == b.tr && a.tag == b.tag &&
-         a.pk == b.pk && a.lit == b.lit && a.esr == b.esr && a.open == b.open;
-}
 
 MarchKernel march_pq_kernel() {
   constexpr MarchVariant v[] = {PERC_MARCH_ROW(PERC_MARCH_PQ)};

@@ -66,9 +66,24 @@ namespace {
 struct Slab {
   int r0 = 0, rows = 0, N = 0, glo = 0, ghi = 0;
   int march_h = 0, march_grid = 0, b_grid = 0, init_grid = 0, red = 0;
-  double *r = nullptr, *p0 = nullptr, *p1 = nullptr, *q = nullptr, *x = nullptr;  // r/p: base row -1
-  double* partials = nullptr;
-  unsigned* tickets = nullptr;
+  DevBuf<double> r, p0, p1, q, x;  // r/p: base row -1
+  DevBuf<double> partials;
+  DevBuf<unsigned> tickets;
+  // the buffers of a slab of b.N rows of m columns, zeroed where the solve reads them first
+  hipError_t alloc(int m, hipStream_t st) {
+    const size_t gpad = 2 * (size_t)m + 8;  // ghost rows + tail pad of the paired loads
+    HIP_TRY(r.alloc(N + gpad));
+    HIP_TRY(p0.alloc(N + gpad));
+    HIP_TRY(p1.alloc(N + gpad));
+    HIP_TRY(q.alloc((size_t)N + 8));
+    HIP_TRY(x.alloc((size_t)N + 8));
+    HIP_TRY(partials.alloc(kRedSlots * red_partials_size(red)));
+    HIP_TRY(tickets.alloc(kRedSlots * red_tickets_size(red)));
+    HIP_TRY(hipMemsetAsync(tickets, 0, kRedSlots * red_tickets_size(red) * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(x, 0, ((size_t)N + 8) * sizeof(double), st));
+    for (double* v : {r.get(), p0.get(), p1.get()}) HIP_TRY(hipMemsetAsync(v, 0, (N + gpad) * sizeof(double), st));
+    return hipSuccess;
+  }
 };
 }  // namespace
 
@@ -79,31 +94,15 @@ hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, 
   const int m = h->g.m, nrows = h->g.n - 2;
   // (the slabs run the row-major q-storing march + streaming B:
   // PERC_MARCH_STRIPS and PERC_MARCH_QFREE do not apply)
-  if (!h->march || K < 1 || K > nrows) return hipErrorInvalidValue;
+  if (!h->plan.march || K < 1 || K > nrows) return hipErrorInvalidValue;
   int cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
   const int spr = m / kMarchW;
   std::vector<Slab> sl(K);
-  hipError_t e = hipSuccess;
-  CGScalars* S = nullptr;
-  CGScalars* hsp = nullptr;
-  auto cleanup = [&]() {
-    for (Slab& b : sl) {
-      for (double* v : {b.r, b.p0, b.p1, b.q, b.x, b.partials}) if (v) (void)hipFree(v);
-      if (b.tickets) (void)hipFree(b.tickets);
-    }
-    if (S) (void)hipFree(S);
-    if (hsp) (void)hipHostFree(hsp);
-  };
-#define SLAB_TRY(x)               \
-  do {                            \
-    e = (x);                      \
-    if (e != hipSuccess) {        \
-      cleanup();                  \
-      return e;                   \
-    }                             \
-  } while (0)
-  const size_t gpad = 2 * (size_t)m + 8;  // ghost rows + tail pad of the paired loads
+  DevBuf<CGScalars> S;
+  PinnedBuf<CGScalars> hsp;
+  int mcus = 0, per_cu = 0;
+  march_occupancy(h, &mcus, &per_cu);
   for (int s = 0, r0 = 0; s < K; ++s) {
     Slab& b = sl[s];
     b.rows = nrows / K + (s < nrows % K ? 1 : 0);
@@ -112,30 +111,22 @@ hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, 
     b.N = b.rows * m;
     b.glo = s > 0 ? -1 : 0;
     b.ghi = s < K - 1 ? b.rows + 1 : b.rows;
-    b.march_h = march_rows_for(h, b.rows);  // as march_geometry picks it for these rows
+    // (as march_geometry picks it for these rows)
+    b.march_h = march_rows_for(m, b.rows, mcus, per_cu, h->march_mode, h->march_rows_req);
     b.march_grid = march_grid_for(spr, b.rows, b.march_h);
     b.b_grid = std::max(1, std::min(2 * cus, cg_grid(b.N)));
     b.init_grid = cg_grid(b.N);
     b.red = std::max({b.march_grid, b.b_grid, b.init_grid});
-    SLAB_TRY(dmalloc(&b.r, b.N + gpad));
-    SLAB_TRY(dmalloc(&b.p0, b.N + gpad));
-    SLAB_TRY(dmalloc(&b.p1, b.N + gpad));
-    SLAB_TRY(dmalloc(&b.q, (size_t)b.N + 8));
-    SLAB_TRY(dmalloc(&b.x, (size_t)b.N + 8));
-    SLAB_TRY(dmalloc(&b.partials, kRedSlots * red_partials_size(b.red)));
-    SLAB_TRY(dmalloc(&b.tickets, kRedSlots * red_tickets_size(b.red)));
-    SLAB_TRY(hipMemsetAsync(b.tickets, 0, kRedSlots * red_tickets_size(b.red) * sizeof(unsigned), st));
-    SLAB_TRY(hipMemsetAsync(b.x, 0, ((size_t)b.N + 8) * sizeof(double), st));
-    for (double* v : {b.r, b.p0, b.p1}) SLAB_TRY(hipMemsetAsync(v, 0, (b.N + gpad) * sizeof(double), st));
+    HIP_TRY(b.alloc(m, st));
   }
-  SLAB_TRY(dmalloc(&S, K));
-  SLAB_TRY(hipHostMalloc(reinterpret_cast<void**>(&hsp), sizeof(CGScalars)));
+  HIP_TRY(S.alloc(K));
+  HIP_TRY(hsp.alloc(1));
   {
     CGScalars s0{};
     s0.tol = tol;
     s0.itmax = itmax;
     std::vector<CGScalars> hs(K, s0);
-    SLAB_TRY(hipMemcpyAsync(S, hs.data(), sizeof(CGScalars) * K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S, hs.data(), sizeof(CGScalars) * K, hipMemcpyHostToDevice, st));
   }
   const CGArgs base = make_cg_args(h);
   auto args = [&](int s) {
@@ -186,54 +177,50 @@ hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, 
   // prologue (x0 = 0: r = b), bnrm and the first bknum over all slabs
   for (int s = 0; s < K; ++s)
     k_cg_init<true><<<sl[s].init_grid, kBlock, 0, st>>>(A[s], itol, 1);
-  SLAB_TRY(dbg_sync(st, "k_cg_init (slabs)"));
+  HIP_TRY(dbg_sync(st, "k_cg_init (slabs)"));
   k_slab_combine<2><<<1, 64, 0, st>>>(S, K, d.err_hist, d.err_hist_cap);
-  SLAB_TRY(halo());
-  int chunk = 8;
-  long long launched = 0;
-  const int kMaxChunk = 256;
+  HIP_TRY(halo());
+  ChunkSchedule cs;
   const MarchKernel march_pq = march_pq_kernel();
   while (true) {
-    for (int j = 0; j < chunk; ++j) {
+    for (int j = 0; j < cs.chunk; ++j) {
       for (int s = 0; s < K; ++s) {
-        A[s].kiter = (int)(launched + j + 1);
+        A[s].kiter = cs.kiter(j);
         march_pq<<<sl[s].march_grid, 64 * kMarchWaves, 0, st>>>(A[s]);
       }
-      SLAB_TRY(dbg_sync(st, "k_cg_march (slabs)"));
+      HIP_TRY(dbg_sync(st, "k_cg_march (slabs)"));
       k_slab_combine<0><<<1, 64, 0, st>>>(S, K, d.err_hist, d.err_hist_cap);
       for (int s = 0; s < K; ++s) {
         if (full_x) k_cg_b<true, true><<<sl[s].b_grid, kBlock, 0, st>>>(A[s]);
         else k_cg_b<true><<<sl[s].b_grid, kBlock, 0, st>>>(A[s]);
       }
-      SLAB_TRY(dbg_sync(st, "k_cg_b (slabs)"));
+      HIP_TRY(dbg_sync(st, "k_cg_b (slabs)"));
       k_slab_combine<1><<<1, 64, 0, st>>>(S, K, d.err_hist, d.err_hist_cap);
-      SLAB_TRY(halo());
+      HIP_TRY(halo());
     }
-    launched += chunk;
-    SLAB_TRY(hipGetLastError());
-    SLAB_TRY(hipMemcpyAsync(hsp, S, sizeof(CGScalars), hipMemcpyDeviceToHost, st));
-    SLAB_TRY(hipStreamSynchronize(st));
-    if (hsp->done || launched > (long long)itmax + 2) break;
-    chunk = std::min(chunk * 2, kMaxChunk);
+    cs.chunk_done();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hsp, S, sizeof(CGScalars), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hsp->done || cs.overrun(itmax)) break;
+    cs.grow();
   }
   // voltages back into the context's x (the currents read rows 0 and N-1)
   const size_t row = sizeof(double) * m;
   if (full_x) {
     for (int s = 0; s < K; ++s)
-      SLAB_TRY(hipMemcpyAsync(d.x + (size_t)sl[s].r0 * m, sl[s].x, row * sl[s].rows,
+      HIP_TRY(hipMemcpyAsync(d.x + (size_t)sl[s].r0 * m, sl[s].x, row * sl[s].rows,
                               hipMemcpyDeviceToDevice, st));
   } else {
-    SLAB_TRY(hipMemcpyAsync(d.x, sl[0].x, row, hipMemcpyDeviceToDevice, st));
-    SLAB_TRY(hipMemcpyAsync(d.x + (size_t)(nrows - 1) * m, sl[K - 1].x + (size_t)(sl[K - 1].rows - 1) * m,
+    HIP_TRY(hipMemcpyAsync(d.x, sl[0].x, row, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.x + (size_t)(nrows - 1) * m, sl[K - 1].x + (size_t)(sl[K - 1].rows - 1) * m,
                             row, hipMemcpyDeviceToDevice, st));
   }
   // the context's scalars as a single-slab solve leaves them
-  SLAB_TRY(hipMemcpyAsync(d.scal, S, sizeof(CGScalars), hipMemcpyDeviceToDevice, st));
-  SLAB_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(d.scal, S, sizeof(CGScalars), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
   *iter = hsp->iter;
   *err = hsp->err;
-  cleanup();
-#undef SLAB_TRY
   return hipSuccess;
 }
 
@@ -250,8 +237,8 @@ hipError_t dev_solve_slabs(perc_ctx* h, int K, int itol, double tol, int itmax, 
 // dev_solve_slabs: K processes give its numbers bitwise.
 struct DSlab {
   Slab b;
-  CGScalars* S = nullptr;
-  CGScalars* hs = nullptr;  // pinned status copy
+  DevBuf<CGScalars> S;
+  PinnedBuf<CGScalars> hs;  // status copy
   CGArgs a;
   perc_dslab_bufs buf{};
   int K = 1, s = 0;
@@ -281,12 +268,7 @@ hipError_t dev_dslab_end(perc_ctx* h, bool to_ctx) {
     if (e == hipSuccess) e = hipStreamSynchronize(st);
   }
   (void)hipStreamSynchronize(st);
-  Slab& b = D->b;
-  for (double* v : {b.r, b.p0, b.p1, b.q, b.x, b.partials}) if (v) (void)hipFree(v);
-  if (b.tickets) (void)hipFree(b.tickets);
-  if (D->S) (void)hipFree(D->S);
-  if (D->hs) (void)hipHostFree(D->hs);
-  delete D;
+  delete D;  // (frees the slab's buffers)
   h->dslab = nullptr;
   return e;
 }
@@ -296,7 +278,7 @@ static hipError_t dslab_setup(perc_ctx* h, int K, int s, int itol, double tol, i
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
   const int m = h->g.m, nrows = h->g.n - 2;
-  if (!h->march || K < 1 || K > nrows || s < 0 || s >= K || !bufs.part_out || !bufs.part_all ||
+  if (!h->plan.march || K < 1 || K > nrows || s < 0 || s >= K || !bufs.part_out || !bufs.part_all ||
       (s > 0 && (!bufs.edge_lo || !bufs.ghost_lo)) || (s < K - 1 && (!bufs.edge_hi || !bufs.ghost_hi)))
     return hipErrorInvalidValue;
   if (d.err_hist_cap < itmax + 2) {
@@ -318,24 +300,16 @@ static hipError_t dslab_setup(perc_ctx* h, int K, int s, int itol, double tol, i
   b.N = b.rows * m;
   b.glo = s > 0 ? -1 : 0;
   b.ghi = s < K - 1 ? b.rows + 1 : b.rows;
-  b.march_h = march_rows_for(h, b.rows);
+  int mcus = 0, per_cu = 0;
+  march_occupancy(h, &mcus, &per_cu);
+  b.march_h = march_rows_for(m, b.rows, mcus, per_cu, h->march_mode, h->march_rows_req);
   b.march_grid = march_grid_for(m / kMarchW, b.rows, b.march_h);
   b.b_grid = std::max(1, std::min(2 * cus, cg_grid(b.N)));
   b.init_grid = cg_grid(b.N);
   b.red = std::max({b.march_grid, b.b_grid, b.init_grid});
-  const size_t gpad = 2 * (size_t)m + 8;
-  HIP_TRY(dmalloc(&b.r, b.N + gpad));
-  HIP_TRY(dmalloc(&b.p0, b.N + gpad));
-  HIP_TRY(dmalloc(&b.p1, b.N + gpad));
-  HIP_TRY(dmalloc(&b.q, (size_t)b.N + 8));
-  HIP_TRY(dmalloc(&b.x, (size_t)b.N + 8));
-  HIP_TRY(dmalloc(&b.partials, kRedSlots * red_partials_size(b.red)));
-  HIP_TRY(dmalloc(&b.tickets, kRedSlots * red_tickets_size(b.red)));
-  HIP_TRY(hipMemsetAsync(b.tickets, 0, kRedSlots * red_tickets_size(b.red) * sizeof(unsigned), st));
-  HIP_TRY(hipMemsetAsync(b.x, 0, ((size_t)b.N + 8) * sizeof(double), st));
-  for (double* v : {b.r, b.p0, b.p1}) HIP_TRY(hipMemsetAsync(v, 0, (b.N + gpad) * sizeof(double), st));
-  HIP_TRY(dmalloc(&D->S, 1));
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&D->hs), sizeof(CGScalars)));
+  HIP_TRY(b.alloc(m, st));
+  HIP_TRY(D->S.alloc(1));
+  HIP_TRY(D->hs.alloc(1));
   CGScalars s0{};
   s0.tol = tol;
   s0.itmax = itmax;

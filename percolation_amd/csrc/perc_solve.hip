@@ -11,6 +11,8 @@
 #include "perc_march.h"
 #include "perc_resident.h"
 
+#include <cstring>
+
 namespace perc {
 namespace {
 
@@ -79,46 +81,16 @@ MarchKernel find_march(const MarchKey& k) {
   return nullptr;
 }
 
-// CUs of the device, and the workgroups a CU holds of the kernel that sizes
-// the bands (PERC_MARCH_OCC)
-void march_occupancy(const perc_ctx* h, int* cus, int* per_cu) {
-  hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, h->device);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, find_march(kMarchOcc), 64 * kMarchWaves, 0);
-}
-
-// The march kernel of a launch: mode kMarchP for the P side (P of the q-free
-// march, else the q-storing P+S), kMarchB for the q-free B.
-//  strip-major pair (the default solve at L <= 4096; phase probe: a.mtrace):
-//    staged edges (B, a.mes) > literal > tagged > trace > plain; with nibble
-//    codes on an open lattice, outside a slab solve, the OPEN twin of each
-//    (march_open: the open-square path alone; the row itself runs under pbc)
-//  row-major pair (vectors past the Infinity Cache): literal and nibble codes
-//    independently (P's nibble codes: a.rm_pnib), B's staged edges without lit
+// (the open-square path of the strip-major nibble kernels: not in a slab solve)
 bool march_open(const CGArgs& a) { return a.sm && a.nib != nullptr && !a.T.pbc && !a.slab; }
-
-MarchKey select_march(int mode, const perc_ctx* h, const CGArgs& a) {
-  if (!h->qfree) return MarchKey{PERC_MARCH_PQ};
-  const bool lit = a.lit != nullptr, nib = a.nib != nullptr, tag = a.mgran != nullptr, tr = a.mtrace != nullptr;
-  if (!a.sm) {
-    if (mode == kMarchP) return {kMarchP, false, kMarchDepth, 0, false, false, nib && a.rm_pnib, lit, 0, false};
-    return {kMarchB, false, kMarchDepth, kNT, false, false, nib, lit, !lit && nib && a.mes ? kEdgeRowsRm : 0, false};
-  }
-  const MarchKey k = {mode, true, 3, kNT, false, false, nib, false, 0, march_open(a)};
-  auto with = [k](bool tr, bool tag, bool lit, int esr) {
-    MarchKey v = k;
-    v.tr = tr, v.tag = tag, v.lit = lit, v.esr = esr;
-    return v;
-  };
-  if (mode == kMarchB && a.mes && !lit && tag) return with(tr, true, false, kEdgeRows);
-  if (lit) return with(false, tag, true, 0);
-  return with(tr, tag, false, 0);
-}
 
 // launch the selected march kernel on its grid (the slot-weighted bands' or
 // the static split's).  A key the table lacks is a programming error: it is
 // reported, never launched as another variant.
 hipError_t launch_march(perc_ctx* h, int mode, hipStream_t st, const CGArgs& a) {
-  const MarchKey k = select_march(mode, h, a);
+  const MarchSel sel = {h->plan.qfree, a.sm != 0,          a.lit != nullptr, a.nib != nullptr, a.mgran != nullptr,
+                        a.mtrace != nullptr, a.mes != 0, a.rm_pnib != 0,   march_open(a)};
+  const MarchKey k = select_march(mode, sel);
   const MarchKernel fn = find_march(k);
   if (!fn) {
     fprintf(stderr, "[perc] march variant {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d} is not compiled\n", k.mode, k.sm,
@@ -131,11 +103,11 @@ hipError_t launch_march(perc_ctx* h, int mode, hipStream_t st, const CGArgs& a) 
 
 // S(k), or the fused P(k)+S(k) of the tiled stencil kernel
 hipError_t launch_cg_spmv(perc_ctx* h, const CGArgs& a, int G) {
-  if (h->fused) {
+  if (h->plan.fused) {
     const int th = h->tile_h;
     const dim3 G2(h->tile_grid), B2(tile_threads(th));
     hipStream_t st = h->stream;
-    if (h->march) return launch_march(h, kMarchP, st, a);
+    if (h->plan.march) return launch_march(h, kMarchP, st, a);
     if (h->g.scn == 4) {
       if (th == 32) klaunch(h, k_cg_ps<4, true, 32>, G2, B2, st, a);
       else if (th == 16) klaunch(h, k_cg_ps<4, true, 16>, G2, B2, st, a);
@@ -145,7 +117,7 @@ hipError_t launch_cg_spmv(perc_ctx* h, const CGArgs& a, int G) {
       else if (th == 16) klaunch(h, k_cg_ps<6, true, 16>, G2, B2, st, a);
       else klaunch(h, k_cg_ps<6, true, 8>, G2, B2, st, a);
     }
-  } else if (!h->stencil) {
+  } else if (!h->plan.stencil) {
     // CSR: one row per thread (k_spmv's row) and the q.p partials
     const int ns = csr_slots(a.A.maxrow), GR = h->row_grid;
     if (ns == 4 && a.A.ecol) klaunch(h, k_cg_spmv_row<-1>, GR, kBlock, h->stream, a);
@@ -161,10 +133,10 @@ hipError_t launch_cg_spmv(perc_ctx* h, const CGArgs& a, int G) {
 // B(k) (streaming; the fused format walks its chunks in reverse)
 hipError_t launch_cg_b(perc_ctx* h, const CGArgs& a, int G) {
   // fused formats: b_grid (set with the lattice, see dev_build_lattice)
-  if (h->fused && h->b_grid > 0) G = h->b_grid;
-  if (h->march && h->qfree) {
+  if (h->plan.fused && h->b_grid > 0) G = h->b_grid;
+  if (h->plan.march && h->plan.qfree) {
     return launch_march(h, kMarchB, h->stream, a);
-  } else if (h->stencil) {
+  } else if (h->plan.stencil) {
     // x on every row with the march's x-in-B (fused, row-major): XF
     if (a.bx && a.xrows == 0 && !a.sm) klaunch(h, k_cg_b<true, true>, G, kBlock, h->stream, a);
     else klaunch(h, k_cg_b<true>, G, kBlock, h->stream, a);
@@ -175,7 +147,7 @@ hipError_t launch_cg_b(perc_ctx* h, const CGArgs& a, int G) {
 }
 
 void launch_spmv(perc_ctx* h, const CGArgs& a, const double* x, double* y) {
-  if (!h->stencil) spmv_launch(h, a.A, x, y, h->stream);
+  if (!h->plan.stencil) spmv_launch(h, a.A, x, y, h->stream);
   else if (h->g.scn == 4) k_spmv_st<4><<<h->grid, kBlock, 0, h->stream>>>(a.St, x, y);
   else k_spmv_st<6><<<h->grid, kBlock, 0, h->stream>>>(a.St, x, y);
 }
@@ -189,25 +161,19 @@ bool sq_nibble_form(const perc_ctx* h) {
   return f >= 0 && f < h->forms.nforms && h->forms.regular[f] && h->forms.rmask[f] == kSqRasterMask;
 }
 
-// the row-major march's nibble codes (vectors past the Infinity Cache, the
-// open square lattice, PERC_MARCH_NIBBLE): 0.5 instead of 2 bytes of row
-// code per element in P and B (24.5 + 48m / N instead of 26 B per row; B
-// 0.297 vs 0.304 ms at L = 8192); a row whose upper code bits are not its
-// column class's keeps the u16 codes.  (pbc lattices keep the u16 codes: the
-// row-major nibble kernels compile the open-square path only)
-hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
+// nibble codes (PERC_MARCH_NIBBLE): the u16 row codes packed two sites per
+// byte into d.nib_sm, strip-major (SM) or row-major; a takes them where every
+// row's upper code bits are its column class's (h->nib_used), else it keeps
+// the u16 codes
+template <bool SM>
+hipError_t pack_nibbles(perc_ctx* h, CGArgs& a) {
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
-  h->nib_used = false;
-  a.rm_pnib = h->knobs.rm_pu16 ? 0 : 1;
-  if (!h->nib_ok || !sq_nibble_form(h) || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) ||
-      !h->march || !h->qfree || a.sm)
-    return hipSuccess;
   const long long n = (long long)a.T.nrows * a.T.m;
   if (!d.nib_sm) HIP_TRY(dmalloc(&d.nib_sm, (size_t)h->N / 2 + 16));
   HIP_TRY(hipMemsetAsync(d.sflag + 3, 0, sizeof(int), st));
-  k_pack_nib<false><<<blocks_for(n / 2), kBlock, 0, st>>>(a.T, d.code, d.nib_sm, h->ncls[0], h->ncls[1],
-                                                          h->ncls[2], d.sflag + 3);
+  k_pack_nib<SM><<<blocks_for(n / 2), kBlock, 0, st>>>(a.T, d.code, d.nib_sm, h->ncls[0], h->ncls[1], h->ncls[2],
+                                                       d.sflag + 3);
   HIP_TRY(dbg_sync(st, "k_pack_nib"));
   int bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, d.sflag + 3, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -215,17 +181,40 @@ hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
   if (!bad) {
     a.nib = d.nib_sm;
     for (int c = 0; c < 3; ++c) a.ncls[c] = h->ncls[c];
-    // the row-major nibble march's P takes its halo columns from the edge
-    // {p, z} pairs its B stores (as the strip-major march), the first P's
-    // from r0
-    const long long ne = 2ll * (a.T.m / kMarchW) * a.T.nrows;
-    if (!d.ez) HIP_TRY(dmalloc(&d.ez, 2 * (size_t)ne + 8));
-    a.ez = d.ez;
-    k_edge_init<<<blocks_for(ne), kBlock, 0, st>>>(a);
-    HIP_TRY(dbg_sync(st, "k_edge_init"));
-    a.mes = a.T.bh <= kEdgeRowsRm && !h->knobs.edge_step ? 1 : 0;  // (B's bands: march_h rows)
   }
   h->nib_used = !bad;
+  return hipSuccess;
+}
+
+// edge {p, z} pairs per strip side and row (the march P's halo columns; its B
+// stores them), the first P's from r0 in a's layout
+hipError_t init_edges(perc_ctx* h, CGArgs& a) {
+  const long long ne = 2ll * (a.T.m / kMarchW) * a.T.nrows;
+  if (!h->d.ez) HIP_TRY(dmalloc(&h->d.ez, 2 * (size_t)ne + 8));
+  a.ez = h->d.ez;
+  k_edge_init<<<blocks_for(ne), kBlock, 0, h->stream>>>(a);
+  return dbg_sync(h->stream, "k_edge_init");
+}
+
+// the row-major march's nibble codes (vectors past the Infinity Cache, the
+// open square lattice, PERC_MARCH_NIBBLE): 0.5 instead of 2 bytes of row
+// code per element in P and B (24.5 + 48m / N instead of 26 B per row; B
+// 0.297 vs 0.304 ms at L = 8192); a row whose upper code bits are not its
+// column class's keeps the u16 codes.  (pbc lattices keep the u16 codes: the
+// row-major nibble kernels compile the open-square path only)
+hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
+  h->nib_used = false;
+  a.rm_pnib = h->knobs.rm_pu16 ? 0 : 1;
+  if (!h->nib_ok || !sq_nibble_form(h) || h->g.pbc || !(h->march_mode & PERC_MARCH_NIBBLE) ||
+      !h->plan.march || !h->plan.qfree || a.sm)
+    return hipSuccess;
+  HIP_TRY(pack_nibbles<false>(h, a));
+  if (h->nib_used) {
+    // the row-major nibble march's P takes its halo columns from the edge
+    // {p, z} pairs its B stores (as the strip-major march)
+    HIP_TRY(init_edges(h, a));
+    a.mes = a.T.bh <= kEdgeRowsRm && !h->knobs.edge_step ? 1 : 0;  // (B's bands: march_h rows)
+  }
   return hipSuccess;
 }
 
@@ -233,7 +222,7 @@ hipError_t to_nib_rows(perc_ctx* h, CGArgs& a) {
 // a B region, each sized for the largest grid either kernel runs; a new
 // solve epoch, so no granule of an earlier solve carries a valid tag
 hipError_t setup_granules(perc_ctx* h, CGArgs& a, int itmax) {
-  if (!h->march_tag || !a.sm || itmax > kTagMaxIter) return hipSuccess;
+  if (!h->plan.march_tag || !a.sm || itmax > kTagMaxIter) return hipSuccess;
   const int GM = std::max(red_grid(h), h->wm_grid);
   const size_t region = (size_t)2 * 2 * ((size_t)GM + red_groups(GM));  // NV <= 2, 16-B granules
   const size_t need = 2 * region;
@@ -260,13 +249,13 @@ hipError_t dev_build_lattice(perc_ctx* h) {
   hipStream_t st = h->stream;
   DeviceBuffers& d = h->d;
   // bond_first
-  int* fc = nullptr;
-  HIP_TRY(dmalloc(&fc, t + 2));
+  DevBuf<int> fc, rc;
+  HIP_TRY(fc.alloc(t + 2));
   HIP_TRY(dmalloc(&d.bond_first, t + 2));
   k_forward_count<<<blocks_for(t + 2), kBlock, 0, st>>>(g, fc);
   HIP_TRY(hipGetLastError());
   HIP_TRY(exclusive_scan(fc, d.bond_first, t + 2, st));
-  HIP_TRY(hipFree(fc));
+  fc.reset();
   h->h_bond_first.resize(t + 2);
   HIP_TRY(hipMemcpy(h->h_bond_first.data(), d.bond_first, sizeof(int) * (t + 2),
                     hipMemcpyDeviceToHost));
@@ -282,13 +271,12 @@ hipError_t dev_build_lattice(perc_ctx* h) {
   for (int c = 0; c + 1 < g.m && h->bf_open_sq; ++c)
     if (h->h_bond_first[(size_t)(g.n - 1) * g.m + c + 1] != (g.n - 1) * (2 * g.m - 1) + c) h->bf_open_sq = false;
   // CSR pattern of the interior block
-  int* rc = nullptr;
-  HIP_TRY(dmalloc(&rc, N + 1));
+  HIP_TRY(rc.alloc(N + 1));
   HIP_TRY(dmalloc(&d.rowptr, N + 1));
   k_row_count<<<blocks_for(N + 1), kBlock, 0, st>>>(g, N, rc);
   HIP_TRY(hipGetLastError());
   HIP_TRY(exclusive_scan(rc, d.rowptr, N + 1, st));
-  HIP_TRY(hipFree(rc));
+  rc.reset();
   int nnz = 0;
   HIP_TRY(hipMemcpy(&nnz, d.rowptr + N, sizeof(int), hipMemcpyDeviceToHost));
   h->nnz = nnz;
@@ -411,62 +399,30 @@ void dev_free_all(perc_ctx* h) {
   h->nnz = 0;
 }
 
-// band height of the register-march kernel over `nrows` rows: the
-// requested height (perc_set_march_rows); vectors past the Infinity Cache:
-// 8-row bands for the row-major march P and B (B 0.310 vs 0.318 ms at 16
-// rows at L = 8192; 16 rows without PERC_MARCH_SLOTS); else one round of
-// resident waves, the height that gives every wave slot of the chip one
-// strip-band
-int march_rows_for(const perc_ctx* h, int nrows) {
-  const Geom& g = h->g;
-  if (h->march_rows_req > 0) return h->march_rows_req;
-  if ((size_t)g.m * nrows * sizeof(double) > kLargeVector)
-    return (h->march_mode & PERC_MARCH_SLOTS) ? 8 : 16;
-  int cus = 0, per_cu = 0;
-  march_occupancy(h, &cus, &per_cu);
-  const long long slots = (long long)std::max(cus, 1) * std::max(per_cu, 1) * kMarchWaves;
-  const long long bands = std::max(1ll, slots / (g.m / kMarchW));
-  return std::max(2, cdiv(nrows, bands));
+// CUs of the device, and the workgroups a CU holds of the kernel that sizes
+// the bands (PERC_MARCH_OCC)
+void march_occupancy(const perc_ctx* h, int* cus, int* per_cu) {
+  hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, h->device);
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, find_march(kMarchOcc), 64 * kMarchWaves, 0);
 }
 
-// band height and grid of the register-march kernel; the slot-weighted
-// bands (PERC_MARCH_SLOTS): one workgroup per CU and round, bands cycling
-// over the rounds, weights = the rounds' relative streaming rates with
-// equal bands (kSlotW: P, B of the strip-major march; same-box A/Bs,
-// profiles/r3_4_ab_slotw_L4096.log; round 6 re-tuned P's for the nibble-code
-// tagged march, whose third slot walked ~2 us longer than the others
-// (profiles/r5_4_mtrace_summary_L4096.txt): 100:76:48 against 100:75:50, P
-// 73.2 vs 75.0 us, 0.1489 vs 0.1511 ms per iteration, r6_4_def_ab_w*.json,
-// r6_5_weights.json; and B's 100:78:55 against 100:80:60 once B stores the
-// edge {p, z}: B 71.6 vs 72.4 us, r6_17_weights.json, r6_18_weights.json).
-// The third set, row-major P past the Infinity Cache, is unused since round
-// 4: that P runs on B's 8-row bands)
-constexpr int kSlotW[3][kMaxSlotRounds] = {{100, 76, 48, 40}, {100, 78, 55, 50}, {100, 100, 100, 100}};
-
+// band height and grid of the register-march kernel, and the slot-weighted
+// bands where the device allows them (the policy: perc_solve_plan.h)
 void march_geometry(perc_ctx* h) {
   const Geom& g = h->g;
   h->march_grid = 0;
   h->wm_slots = 0;
   h->wm_grid = 0;
   if (g.m % kMarchW != 0 || g.n <= 2) return;
-  const int spr = g.m / kMarchW, nrows = g.n - 2;
-  h->march_h = march_rows_for(h, nrows);
-  h->march_grid = march_grid_for(spr, nrows, h->march_h);
+  const int nrows = g.n - 2;
   int cus = 0, per_cu = 0;
   march_occupancy(h, &cus, &per_cu);
-  const long long waves = (long long)cus * kMarchWaves;
-  const int(*wts)[kMaxSlotRounds] = h->slot_w_set ? h->slot_w : kSlotW;
-  bool ok = cus > 0 && per_cu >= 2 && per_cu <= kMaxSlotRounds && waves % spr == 0 &&
-            (waves / spr) * per_cu <= nrows;
-  for (int i = 0; ok && i < per_cu; ++i) ok = wts[0][i] > 0 && wts[1][i] > 0 && wts[2][i] > 0;
-  if (ok) {
-    h->wm_slots = per_cu;
-    h->wm_grid = cus * per_cu;
-    for (int k = 0; k < 3; ++k) {
-      h->wm_cum[k][0] = 0;
-      for (int i = 0; i < per_cu; ++i) h->wm_cum[k][i + 1] = h->wm_cum[k][i] + wts[k][i];
-    }
-  }
+  h->march_h = march_rows_for(g.m, nrows, cus, per_cu, h->march_mode, h->march_rows_req);
+  h->march_grid = march_grid_for(g.m / kMarchW, nrows, h->march_h);
+  const SlotGeometry s = slot_geometry(g.m, nrows, cus, per_cu, h->slot_w_set ? h->slot_w : kSlotW);
+  h->wm_slots = s.slots;
+  h->wm_grid = s.grid;
+  std::memcpy(h->wm_cum, s.cum, sizeof(s.cum));
 }
 
 // resident solve: m a multiple of 1024 (MT = m / 1024 columns per thread
@@ -497,47 +453,15 @@ void res_geometry(perc_ctx* h) {
     if (!h->forms.regular[f]) return;  // wrapped columns (pbc): slot order is not raster order
   h->res_MT = MT;
   h->res_H = H;
-  h->res_HMAX = MT == 1 ? 4 : 8;
   h->res_G = cdiv(nrows, H);
 }
 
 // solver kernels for the requested format and what the assembly allows
 void select_format(perc_ctx* h) {
-  h->stencil = h->fmt_req != PERC_FMT_CSR && h->stencil_ok;
-  h->fused = h->stencil && h->tiled_ok && h->fmt_req != PERC_FMT_STENCIL_SPLIT;
-  h->march = h->fused && h->march_ok && h->fmt_req != PERC_FMT_STENCIL_TILED;
-  // the literal dot order runs the production kernels: the q-free march and
-  // the resident solve store their rows' dot terms (a.lit / ResArgs::lit,
-  // 3 N doubles addressed by 32-bit buffer offsets: < 2 GB), which the
-  // serial folds sum; past that size the q-storing march (the folds then
-  // form the terms from q, p, r)
-  const bool literal = h->dot_order != PERC_DOT_FAST;
-  const bool lit_ok = !literal || (size_t)h->N * 24 < ((size_t)1 << 31);
-  // (dev_solve only: the march kernels stay selected for the probes; the
-  // host-folded literal order runs the launched march, whose kernels the
-  // host can fold between)
-  h->resident = h->fused && h->res_G > 0 && h->fmt_req != PERC_FMT_STENCIL_TILED &&
-                (h->march_mode & PERC_SOLVE_RESIDENT) && h->march_rows_req == 0 && lit_ok &&
-                h->dot_order != PERC_DOT_LITERAL_HOST;
-  h->qfree = h->march && (h->march_mode & PERC_MARCH_QFREE) && lit_ok;
-  h->march_alt = h->march && (h->march_mode & PERC_MARCH_ALT);
-  // one-workgroup solve for small systems, under the default format only
-  // (an explicit format keeps its launched kernels, e.g. for the tests)
-  h->small = h->fmt_req == PERC_FMT_AUTO && h->N > 0 && h->N <= kSmallRows &&
-             (h->march_mode & PERC_SOLVE_RESIDENT) && h->d.rowptr != nullptr;
-  // strip-major q-free march only while a vector fits the Infinity Cache
-  // (L <= 4096): past it the row-major march is faster (L = 8192, round 4
-  // with nibble codes and slot bands: 0.652 vs 0.734 ms per iteration,
-  // profiles/r4_4_l8192_strips_ab.json; round 2: 0.439 vs 0.480 ms); its
-  // whole-array buffer views also need < 2 GB
-  h->strips = h->qfree && (h->march_mode & PERC_MARCH_STRIPS) && (size_t)h->N * sizeof(double) <= kLargeVector;
-  // slot-weighted bands of the strip-major march (to_strips applies them)
-  const bool slots = (h->march_mode & PERC_MARCH_SLOTS) != 0;
-  h->march_slots = slots && h->strips && h->wm_slots > 0;
-  // tagged-granule reductions of the strip-major march (PERC_MARCH_TAG);
-  // their tags are (epoch << 24) | iteration, so solves of >= 2^24 - 2
-  // iterations take the ticket reduction
-  h->march_tag = (h->march_mode & PERC_MARCH_TAG) && h->strips;
+  const SolveRequest req = {h->fmt_req, h->march_mode, h->dot_order, h->march_rows_req};
+  const SolveFacts facts = {h->N,     h->stencil_ok, h->tiled_ok,           h->march_ok,
+                            h->res_G, h->wm_slots,   h->d.rowptr != nullptr};
+  h->plan = solve_plan(req, facts);
 }
 
 // strip-major copies of r (into the q buffer: r and q swap roles for the
@@ -555,32 +479,12 @@ hipError_t to_strips(perc_ctx* h, CGArgs& a) {
   a.St.code = d.code_sm;
   a.sm = 1;
   a.bx = 1;  // x (row-major) is updated in the q-free march B
-  // edge {p, z} (the march P's halo columns), the first P's from r0 (the
-  // strip-major r and codes: a.sm set)
-  const long long ne = 2ll * (a.T.m / kMarchW) * a.T.nrows;
-  if (!d.ez) HIP_TRY(dmalloc(&d.ez, 2 * (size_t)ne + 8));  // {p, z} pairs
-  a.ez = d.ez;
-  k_edge_init<<<blocks_for(ne), kBlock, 0, st>>>(a);
-  HIP_TRY(dbg_sync(st, "k_edge_init"));
+  HIP_TRY(init_edges(h, a));  // (from the strip-major r and codes: a.sm set)
   // nibble codes (PERC_MARCH_NIBBLE, square lattice): 0.5 instead of 2
   // bytes of row code per element in both march kernels
   h->nib_used = false;
-  if (h->nib_ok && sq_nibble_form(h) && (h->march_mode & PERC_MARCH_NIBBLE)) {
-    if (!d.nib_sm) HIP_TRY(dmalloc(&d.nib_sm, (size_t)h->N / 2 + 16));
-    HIP_TRY(hipMemsetAsync(d.sflag + 3, 0, sizeof(int), st));
-    k_pack_nib<true><<<blocks_for(n / 2), kBlock, 0, st>>>(a.T, d.code, d.nib_sm, h->ncls[0], h->ncls[1],
-                                                           h->ncls[2], d.sflag + 3);
-    HIP_TRY(dbg_sync(st, "k_pack_nib"));
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, d.sflag + 3, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!bad) {
-      a.nib = d.nib_sm;
-      for (int c = 0; c < 3; ++c) a.ncls[c] = h->ncls[c];
-    }
-    h->nib_used = !bad;
-  }
-  if (h->march_slots) {
+  if (h->nib_ok && sq_nibble_form(h) && (h->march_mode & PERC_MARCH_NIBBLE)) HIP_TRY(pack_nibbles<true>(h, a));
+  if (h->plan.march_slots) {
     a.wslots = h->wm_slots;
     for (int i = 0; i <= h->wm_slots; ++i) {
       a.wcum[0][i] = h->wm_cum[0][i];
@@ -774,7 +678,7 @@ MarchKnobs read_march_knobs() {
 // is carried, and what perc_last_solve reports.  probe: perc_bench_kernel's
 // steady-state launches of the same kernels (no solve: last_flags stays).
 hipError_t prepare_march(perc_ctx* h, CGArgs& a, int itmax, bool probe) {
-  if (h->strips) HIP_TRY(to_strips(h, a));
+  if (h->plan.strips) HIP_TRY(to_strips(h, a));
   else HIP_TRY(to_nib_rows(h, a));
   HIP_TRY(setup_granules(h, a, itmax));
   // x on the electrode-side rows, each iteration's update applied by the
@@ -785,9 +689,9 @@ hipError_t prepare_march(perc_ctx* h, CGArgs& a, int itmax, bool probe) {
   if (probe) return hipSuccess;
   const bool host_fold = a.lit && h->dot_order == PERC_DOT_LITERAL_HOST;
   h->last_flags = (h->dot_order != PERC_DOT_FAST ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0) |
-                  (h->march && h->qfree ? PERC_RAN_QFREE : 0) | (a.sm ? PERC_RAN_STRIPS : 0) |
+                  (h->plan.march && h->plan.qfree ? PERC_RAN_QFREE : 0) | (a.sm ? PERC_RAN_STRIPS : 0) |
                   (a.nib ? PERC_RAN_NIBBLE : 0) | (a.mgran ? PERC_RAN_TAG : 0) |
-                  (host_fold ? PERC_RAN_HOST_FOLD : 0) | (h->march && h->qfree && march_open(a) ? PERC_RAN_OPEN : 0);
+                  (host_fold ? PERC_RAN_HOST_FOLD : 0) | (h->plan.march && h->plan.qfree && march_open(a) ? PERC_RAN_OPEN : 0);
   return hipSuccess;
 }
 }  // namespace
@@ -812,10 +716,7 @@ namespace {
 // CPU's add latency instead of a GPU wave's (~17 cycles per dependent fp64
 // add, tools/fold_bench.hip).
 struct HostFold {
-  double* t = nullptr;  // pinned, 3 N
-  ~HostFold() {
-    if (t) (void)hipHostFree(t);
-  }
+  PinnedBuf<double> t;  // 3 N
 };
 hipError_t host_fold_qp(perc_ctx* h, const CGArgs& a, HostFold& hf) {
   const int N = h->N;
@@ -825,7 +726,7 @@ hipError_t host_fold_qp(perc_ctx* h, const CGArgs& a, HostFold& hf) {
   HIP_TRY(hipMemcpyAsync(hf.t, a.lit, sizeof(double) * N, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (s.done) return hipSuccess;
-  const double* __restrict__ t = hf.t;
+  const double* __restrict__ t = hf.t.get();
   double acc = 0.0;
   for (int j = 0; j < N; ++j) acc = acc + t[j];  // akden, bondc.f:803-805
   s.akden = acc;
@@ -959,14 +860,6 @@ __global__ __launch_bounds__(kBlock) void k_x34_upd(CsrView A, double* __restric
   x34_block<4, MAXN>(v, out);
 }
 
-struct X34Scratch {
-  double *r = nullptr, *p = nullptr, *q = nullptr, *part = nullptr;
-  ~X34Scratch() {
-    for (double* v : {r, p, q, part})
-      if (v) (void)hipFree(v);
-  }
-};
-
 hipError_t dev_solve_x34(perc_ctx* h, int itol, double tol, int itmax, int* iter, double* err) {
   HIP_TRY(ensure_csr(h));
   if (!h->csr_ok) {
@@ -978,11 +871,13 @@ hipError_t dev_solve_x34(perc_ctx* h, int itol, double tol, int itmax, int* iter
   hipStream_t st = h->stream;
   const CsrView A = make_cg_args(h).A;
   const int G = std::max(1, std::min(kX34Grid, cdiv(N, kBlock)));
-  X34Scratch w;
-  HIP_TRY(dmalloc(&w.r, (size_t)N));
-  HIP_TRY(dmalloc(&w.p, (size_t)N));
-  HIP_TRY(dmalloc(&w.q, (size_t)N));
-  HIP_TRY(dmalloc(&w.part, (size_t)4 * G));
+  struct {
+    DevBuf<double> r, p, q, part;
+  } w;
+  HIP_TRY(w.r.alloc((size_t)N));
+  HIP_TRY(w.p.alloc((size_t)N));
+  HIP_TRY(w.q.alloc((size_t)N));
+  HIP_TRY(w.part.alloc((size_t)4 * G));
   std::vector<double> part(4 * (size_t)G);
   double sum[4];
   // the literal dot orders (perc_set_dot_order, linbcg_'s default): the
@@ -1154,8 +1049,8 @@ int forms_row_reach(const StencilForms& F) {
 }
 
 bool front_allowed(const perc_ctx* h, const CGArgs& a, bool x0_zero) {
-  return x0_zero && h->knobs.front && !h->knobs.trace && h->nslab <= 1 && !a.slab && h->stencil && h->march &&
-         h->qfree && a.T.m > 0 && a.T.nrows > 0 && (long long)a.T.m * a.T.nrows == h->N &&
+  return x0_zero && h->knobs.front && !h->knobs.trace && h->nslab <= 1 && !a.slab && h->plan.stencil && h->plan.march &&
+         h->plan.qfree && a.T.m > 0 && a.T.nrows > 0 && (long long)a.T.m * a.T.nrows == h->N &&
          forms_row_reach(h->forms) == 1;
 }
 
@@ -1191,16 +1086,101 @@ void front_rows(const perc_ctx* h, MarchFront& F, CGArgs& a) {
   if (front_dead_band(h, a, 0) || front_dead_band(h, a, 1)) F.last_dead = k;
 }
 
-hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,
-                          int* iter, double* err) {
+// Kernel timing of the launch loop: per timed iteration the start / stop
+// events of P, S and B, recorded by the kernels' own dispatch packets
+// (klaunch).  Every `every`-th iteration of a chunk is sampled: 64 (a timed
+// launch's event packets open a dispatch gap of several us: every 8th
+// iteration timed cost ~1 us per iteration on average,
+// profiles/r6_43_march_gaps.txt; MarchKnobs::time_every overrides)
+struct IterTiming {
+  enum Phase { kP = 0, kS = 1, kB = 2 };
+  static constexpr int kEv = 6;  // events per iteration slot of a chunk
+  perc_ctx* h;
+  KernelTiming& T;
+  const int every;
+  explicit IterTiming(perc_ctx* ctx) : h(ctx), T(ctx->timing), every(ctx->knobs.time_every) {}
+  hipError_t init() {  // events for the longest chunk
+    if (!T.enabled || T.ev.size() >= kEv * (size_t)ChunkSchedule::kMax) return hipSuccess;
+    const size_t have = T.ev.size();
+    T.ev.resize(kEv * (size_t)ChunkSchedule::kMax);
+    for (size_t i = have; i < T.ev.size(); ++i) HIP_TRY(timing_event_create(&T.ev[i]));
+    return hipSuccess;
+  }
+  // the next CG launch is iteration slot j's `phase`: it carries the events if j is sampled
+  void arm(int j, Phase phase) {
+    if (!T.enabled || j % every != 0) return;
+    h->ev_next[0] = T.ev[kEv * j + 2 * phase];
+    h->ev_next[1] = T.ev[kEv * j + 2 * phase + 1];
+  }
+  void disarm() { h->ev_next[0] = h->ev_next[1] = nullptr; }
+  // after the chunk's synchronize: the sampled launches among its first
+  // `real` iterations (the launches of this chunk that did work)
+  void collect(int real) {
+    if (!T.enabled) return;
+    int nt = 0;
+    for (int j = 0; j < real; j += every, ++nt) {
+      float tp = 0.f, ts = 0.f, tb = 0.f;
+      if (!h->plan.fused) hipEventElapsedTime(&tp, T.ev[kEv * j], T.ev[kEv * j + 1]);
+      hipEventElapsedTime(&ts, T.ev[kEv * j + 2], T.ev[kEv * j + 3]);
+      hipEventElapsedTime(&tb, T.ev[kEv * j + 4], T.ev[kEv * j + 5]);
+      T.p_ms += tp;
+      T.spmv_ms += ts;
+      T.update_ms += tb;
+    }
+    T.spmv_n += nt;
+    T.update_n += nt;
+    T.p_n += nt;
+  }
+};
+
+// Phase probe of the strip-major march (MarchKnobs::trace): per-wave stamps
+// (4 words) of the P and B launches of iterations first_it (default 1000) ..
+// +3, appended to the CSV at `path` after the solve
+struct MarchTrace {
+  static constexpr int kIters = 4;  // traced iterations
+  DevBuf<unsigned long long> buf;
+  const char* path = nullptr;
+  int first_it = 0;
+  size_t waves = 0;
+  size_t words() const { return (size_t)2 * kIters * 4 * waves; }
+  hipError_t alloc(const perc_ctx* h) {
+    path = h->knobs.trace;
+    first_it = h->knobs.trace_it;
+    waves = (size_t)std::max(h->march_grid, h->wm_grid) * kMarchWaves;
+    HIP_TRY(buf.alloc(words()));
+    return hipMemsetAsync(buf, 0, words() * 8, h->stream);
+  }
+  // the stamps of launch kiter's P (kb = 0) or B (1); null outside the traced iterations
+  unsigned long long* slot(int kiter, int kb) const {
+    const int it = kiter - first_it;
+    return buf && it >= 0 && it < kIters ? buf + (size_t)(2 * it + kb) * 4 * waves : nullptr;
+  }
+  hipError_t dump(const perc_ctx* h) const {
+    if (!buf) return hipSuccess;
+    std::vector<unsigned long long> tr(words());
+    HIP_TRY(hipMemcpy(tr.data(), buf, tr.size() * 8, hipMemcpyDeviceToHost));
+    if (FILE* fo = fopen(path, "a")) {
+      fprintf(fo, "# m=%d nrows=%d band_rows=%d grid=%d waves=%zu (wall clock ticks, 100 MHz)\n"
+                  "iter,kernel,wave,t_entry,t_walk_end,t_exit,xcc,hw_id\n",
+              h->g.m, h->g.n - 2, h->march_h, h->march_grid, waves);
+      for (int it = 0; it < kIters; ++it)
+        for (int kb = 0; kb < 2; ++kb)
+          for (size_t wv = 0; wv < waves; ++wv) {
+            const unsigned long long* v = &tr[((size_t)(2 * it + kb) * waves + wv) * 4];
+            fprintf(fo, "%d,%s,%zu,%llu,%llu,%llu,%llu,%llu\n", first_it + it, kb ? "B" : "P", wv, v[0],
+                    v[1], v[2], v[3] >> 32, v[3] & 0xffffffffull);
+          }
+      fclose(fo);
+    }
+    return hipSuccess;
+  }
+};
+
+// the solve's scalars, tickets and error history; x = 0 when it starts there
+hipError_t reset_scalars(perc_ctx* h, double tol, int itmax, bool x0_zero) {
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
-  const bool literal = h->dot_order != PERC_DOT_FAST;
-  if (literal && h->nslab > 1) {
-    set_error("the literal dot order sums over the whole system: one slab only");
-    return hipErrorInvalidValue;
-  }
-  if (!h->stencil) HIP_TRY(ensure_csr(h));
+  if (!h->plan.stencil) HIP_TRY(ensure_csr(h));
   if (d.err_hist_cap < itmax + 2) {
     if (d.err_hist) HIP_TRY(hipFree(d.err_hist));
     d.err_hist_cap = itmax + 2;
@@ -1218,6 +1198,187 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
   if (x0_zero) {
     k_zero<<<blocks_for(h->N + 2), kBlock, 0, st>>>(d.x, h->N + 2);
   }
+  return hipSuccess;
+}
+
+// r(0), bnrm and the first bknum (k_cg_init; the literal order: in ascending
+// j), and where the literal order's production kernels store their terms
+hipError_t solve_prologue(perc_ctx* h, CGArgs& a, int itol, bool x0_zero) {
+  DeviceBuffers& d = h->d;
+  hipStream_t st = h->stream;
+  const bool literal = h->dot_order != PERC_DOT_FAST, ST = h->plan.stencil;
+  if (ST) k_cg_init<true><<<h->grid, kBlock, 0, st>>>(a, itol, x0_zero ? 1 : 0);
+  else k_cg_init<false><<<h->grid, kBlock, 0, st>>>(a, itol, x0_zero ? 1 : 0);
+  HIP_TRY(dbg_sync(st, "k_cg_init"));
+  if (literal) {  // bnrm and the first bknum in ascending j
+    if (ST) k_fold_init<true><<<1, 64, 0, st>>>(a, itol);
+    else k_fold_init<false><<<1, 64, 0, st>>>(a, itol);
+    HIP_TRY(dbg_sync(st, "k_fold_init"));
+  }
+  // the production kernels in the literal order store their terms (a.lit):
+  // the q-free march and the resident solve
+  if (literal && !h->plan.small && (h->plan.resident || (h->plan.march && h->plan.qfree))) {
+    if (!d.lit) HIP_TRY(dmalloc(&d.lit, (size_t)3 * h->N + 8));
+    a.lit = d.lit;
+  }
+  return hipSuccess;
+}
+
+// The solves that are one kernel: the one-workgroup solve (k_cg_small) and the
+// resident cooperative solve.  *done stays false where neither applies, or the
+// resident launch was refused and the launched kernels take over.
+hipError_t solve_one_kernel(perc_ctx* h, const CGArgs& a, int* iter, double* err, bool* done) {
+  hipStream_t st = h->stream;
+  const bool literal = h->dot_order != PERC_DOT_FAST, ST = h->plan.stencil;
+  *done = false;
+  if (!h->plan.small && !h->plan.resident) return hipSuccess;
+  // (the one-kernel solves' flags; the launched kernels': prepare_march)
+  h->last_flags = (literal ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0);
+  if (h->plan.small) {  // one workgroup runs the whole loop (k_cg_small)
+    // (x is kept on every row here: the operator is the CSR one and N small)
+    if (ST) {
+      if (literal) k_cg_small<true, true><<<1, kSmallThreads, 0, st>>>(a);
+      else k_cg_small<true, false><<<1, kSmallThreads, 0, st>>>(a);
+    } else {
+      if (literal) k_cg_small<false, true><<<1, kSmallThreads, 0, st>>>(a);
+      else k_cg_small<false, false><<<1, kSmallThreads, 0, st>>>(a);
+    }
+    HIP_TRY(dbg_sync(st, "k_cg_small"));
+    CGScalars hs{};
+    HIP_TRY(hipMemcpyAsync(&hs, h->d.scal, sizeof(hs), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *iter = hs.iter;
+    *err = hs.err;
+    *done = true;
+    return hipSuccess;
+  }
+  const hipError_t e = dev_solve_resident(h, a, iter, err);
+  // the cooperative launch can be refused when the grid cannot be
+  // co-resident (e.g. CUs taken by another context): nothing ran, r and
+  // the scalars are as k_cg_init left them, so the launched kernels take
+  // over for this solve
+  if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorInvalidConfiguration) {
+    *done = true;
+    return e;
+  }
+  (void)hipGetLastError();
+  fprintf(stderr, "[perc] resident solve not launchable (%s): launched kernels\n",
+          hipGetErrorString(e));
+  h->plan.resident = false;
+  h->last_kernel = h->plan.family();
+  return hipSuccess;
+}
+
+// the x updates the loop left pending (a solve that ran an iteration)
+hipError_t finish_x(perc_ctx* h, const CGArgs& a) {
+  hipStream_t st = h->stream;
+  if (!a.bx) {
+    k_cg_xfinal<<<h->grid, kBlock, 0, st>>>(a);
+    HIP_TRY(dbg_sync(st, "k_cg_xfinal"));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (a.mxin) {  // the last B's x update
+    k_march_xpend<<<cdiv(2 * h->g.m, kBlock), kBlock, 0, st>>>(a);
+    HIP_TRY(dbg_sync(st, "k_march_xpend"));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return hipSuccess;
+}
+
+// The launched kernels: iterations in chunks (ChunkSchedule); the device flag
+// makes the launches past the stop no-ops
+hipError_t solve_launched(perc_ctx* h, CGArgs& a, int itmax, bool x0_zero, int* iter, double* err) {
+  hipStream_t st = h->stream;
+  const bool literal = h->dot_order != PERC_DOT_FAST, ST = h->plan.stencil;
+  const int G = h->grid;
+  if (!(h->plan.march && h->plan.qfree)) a.lit = nullptr;  // (the other kernels store no terms)
+  HIP_TRY(prepare_march(h, a, itmax, false));
+  MarchFront front;
+  front.on = front_allowed(h, a, x0_zero);
+  if (front.on) h->last_flags |= PERC_RAN_FRONT;
+  HostFold hf;
+  const bool host_fold = (h->last_flags & PERC_RAN_HOST_FOLD) != 0;
+  if (host_fold) HIP_TRY(hf.t.alloc(3 * (size_t)h->N));
+  PinnedBuf<CGScalars> hsp;
+  HIP_TRY(hsp.alloc(1));
+  IterTiming timing(h);
+  HIP_TRY(timing.init());
+  MarchTrace trace;
+  if (h->knobs.trace && h->plan.march && a.sm && h->plan.qfree) HIP_TRY(trace.alloc(h));
+  ChunkSchedule cs;
+  int done_iters = 0;
+  while (true) {
+    for (int j = 0; j < cs.chunk; ++j) {
+      a.kiter = cs.kiter(j);
+      front_rows(h, front, a);
+      // (tag: exact in a double while solve_epoch < 2^29)
+      a.mtag = (double)(((unsigned long long)h->solve_epoch << 24) | (unsigned long long)a.kiter);
+      a.mtrace = trace.slot(a.kiter, 0);
+      if (!h->plan.fused) {
+        timing.arm(j, IterTiming::kP);
+        if (ST) klaunch(h, k_cg_p<true>, G, kBlock, st, a);
+        else klaunch(h, k_cg_p<false>, G, kBlock, st, a);
+        HIP_TRY(dbg_sync(st, "k_cg_p"));
+      }
+      timing.arm(j, IterTiming::kS);
+      HIP_TRY(launch_cg_spmv(h, a, G));
+      HIP_TRY(dbg_sync(st, "k_cg_spmv"));
+      if (host_fold) {  // akden in ascending j, then ak (on the host)
+        HIP_TRY(host_fold_qp(h, a, hf));
+      } else if (literal) {  // akden in ascending j, then ak
+        k_fold_qp<<<1, 64, 0, st>>>(a);
+        HIP_TRY(dbg_sync(st, "k_fold_qp"));
+      }
+      timing.arm(j, IterTiming::kB);
+      a.mtrace = trace.slot(a.kiter, 1);
+      HIP_TRY(launch_cg_b(h, a, G));
+      a.mtrace = nullptr;
+      HIP_TRY(dbg_sync(st, "k_cg_b"));
+      timing.disarm();
+      if (host_fold) {  // z.r and r.r in ascending j: bk, err, the stop test (host)
+        HIP_TRY(host_fold_b(h, a, hf));
+      } else if (literal) {  // z.r and r.r in ascending j: bk, err, the stop test
+        if (ST) k_fold_b<true><<<1, 64, 0, st>>>(a);
+        else k_fold_b<false><<<1, 64, 0, st>>>(a);
+        HIP_TRY(dbg_sync(st, "k_fold_b"));
+      }
+    }
+    cs.chunk_done();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hsp, h->d.scal, sizeof(CGScalars), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    timing.collect(std::min(cs.chunk, hsp->iter - done_iters));
+    done_iters = hsp->iter;
+    if (hsp->done) break;
+    // the first chunk walked every band; its read-back brings the source rows
+    if (front.on && cs.first_done() && hsp->rhi >= hsp->rlo) {
+      front.lo = hsp->rlo / a.T.m;
+      front.hi = hsp->rhi / a.T.m;
+      front.known = front.hi < a.T.nrows;
+    }
+    if (cs.overrun(itmax)) break;
+    cs.grow();
+  }
+  if (hsp->iter > 0) HIP_TRY(finish_x(h, a));
+  HIP_TRY(trace.dump(h));
+  *iter = hsp->iter;
+  *err = hsp->err;
+  // iterations that ran with a dead band (the launches past the stop did nothing)
+  h->last_front = std::max(0, std::min(hsp->iter, front.last_dead) - ChunkSchedule::kFirst);
+  if (a.mgran && hsp->pad[1] != 0) {
+    fprintf(stderr, "[perc] k_cg_march: reduction granule not seen within the poll limit\n");
+    return hipErrorLaunchTimeOut;
+  }
+  return hipSuccess;
+}
+
+hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_zero, bool full_x,
+                          int* iter, double* err) {
+  if (h->dot_order != PERC_DOT_FAST && h->nslab > 1) {
+    set_error("the literal dot order sums over the whole system: one slab only");
+    return hipErrorInvalidValue;
+  }
+  HIP_TRY(reset_scalars(h, tol, itmax, x0_zero));
   if (itol >= 3) return dev_solve_x34(h, itol, tol, itmax, iter, err);
   // row slabs (perc_set_slabs; the prologue starts from x = 0, as linbcg's
   // callers do)
@@ -1232,213 +1393,17 @@ hipError_t dev_solve_impl(perc_ctx* h, int itol, double tol, int itmax, bool x0_
   // is carried on the first and last lattice rows only -- bitwise the same
   // values there, 16 B/row/iteration less traffic
   a.xrows = full_x || h->g.m <= 0 ? 0 : h->g.m;
-  const int G = h->grid;
-  const bool ST = h->stencil;
-  if (ST) k_cg_init<true><<<G, kBlock, 0, st>>>(a, itol, x0_zero ? 1 : 0);
-  else k_cg_init<false><<<G, kBlock, 0, st>>>(a, itol, x0_zero ? 1 : 0);
-  HIP_TRY(dbg_sync(st, "k_cg_init"));
-  if (literal) {  // bnrm and the first bknum in ascending j
-    if (ST) k_fold_init<true><<<1, 64, 0, st>>>(a, itol);
-    else k_fold_init<false><<<1, 64, 0, st>>>(a, itol);
-    HIP_TRY(dbg_sync(st, "k_fold_init"));
-  }
-  // the production kernels in the literal order store their terms (a.lit):
-  // the q-free march and the resident solve
-  if (literal && !h->small && (h->resident || (h->march && h->qfree))) {
-    if (!d.lit) HIP_TRY(dmalloc(&d.lit, (size_t)3 * h->N + 8));
-    a.lit = d.lit;
-  }
-  h->last_kernel = h->small ? PERC_RAN_SMALL : (h->resident ? PERC_RAN_RESIDENT : (h->march ? PERC_RAN_MARCH : 0));
-  // (the one-kernel solves' flags; the launched kernels': prepare_march)
-  if (h->small || h->resident) h->last_flags = (literal ? PERC_RAN_LITERAL : 0) | (a.lit ? PERC_RAN_LIT_TERMS : 0);
-  if (h->small) {  // one workgroup runs the whole loop (k_cg_small)
-    // (x is kept on every row here: the operator is the CSR one and N small)
-    if (ST) {
-      if (literal) k_cg_small<true, true><<<1, kSmallThreads, 0, st>>>(a);
-      else k_cg_small<true, false><<<1, kSmallThreads, 0, st>>>(a);
-    } else {
-      if (literal) k_cg_small<false, true><<<1, kSmallThreads, 0, st>>>(a);
-      else k_cg_small<false, false><<<1, kSmallThreads, 0, st>>>(a);
-    }
-    HIP_TRY(dbg_sync(st, "k_cg_small"));
-    CGScalars hs{};
-    HIP_TRY(hipMemcpyAsync(&hs, d.scal, sizeof(hs), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *iter = hs.iter;
-    *err = hs.err;
-    return hipSuccess;
-  }
-  if (h->resident) {
-    const hipError_t e = dev_solve_resident(h, a, iter, err);
-    // the cooperative launch can be refused when the grid cannot be
-    // co-resident (e.g. CUs taken by another context): nothing ran, r and
-    // the scalars are as k_cg_init left them, so the launched kernels take
-    // over for this solve
-    if (e != hipErrorCooperativeLaunchTooLarge && e != hipErrorInvalidConfiguration) return e;
-    (void)hipGetLastError();
-    fprintf(stderr, "[perc] resident solve not launchable (%s): launched kernels\n",
-            hipGetErrorString(e));
-    h->resident = false;
-    h->last_kernel = h->march ? PERC_RAN_MARCH : 0;
-  }
-  if (!(h->march && h->qfree)) a.lit = nullptr;  // (the other kernels store no terms)
-  HIP_TRY(prepare_march(h, a, itmax, false));
-  MarchFront front;
-  front.on = front_allowed(h, a, x0_zero);
-  if (front.on) h->last_flags |= PERC_RAN_FRONT;
-  HostFold hf;
-  const bool host_fold = (h->last_flags & PERC_RAN_HOST_FOLD) != 0;
-  if (host_fold) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hf.t), sizeof(double) * 3 * (size_t)h->N));
-  // iterate in chunks; the device flag makes surplus launches no-ops
-  constexpr int kFirstChunk = 8;
-  int chunk = kFirstChunk;
-  CGScalars* hsp = nullptr;
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hsp), sizeof(CGScalars)));
-  hipError_t e = hipSuccess;
-  long long launched = 0;
-  KernelTiming& T = h->timing;
-  const int kMaxChunk = 256;
-  // per timed iteration: start/stop of P, S and B, recorded by the
-  // kernels' own dispatch packets (klaunch)
-  constexpr int kEv = 6;
-  if (T.enabled && T.ev.size() < kEv * (size_t)kMaxChunk) {
-    const size_t have = T.ev.size();
-    T.ev.resize(kEv * (size_t)kMaxChunk);
-    for (size_t i = have; i < T.ev.size(); ++i) HIP_TRY(timing_event_create(&T.ev[i]));
-  }
-  int done_iters = 0;
-  // kernel timing samples every kTimeEvery-th iteration of a chunk: 64 (a
-  // timed launch's event packets open a dispatch gap of several us: every
-  // 8th iteration timed cost ~1 us per iteration on average,
-  // profiles/r6_43_march_gaps.txt; MarchKnobs::time_every overrides)
-  const int kTimeEvery = h->knobs.time_every;
-  // phase probe (MarchKnobs::trace): per-wave stamps of the P and B launches
-  // of iterations trace_it (default 1000) .. +3
-  const char* mtpath = h->knobs.trace;
-  const int mt_it = h->knobs.trace_it;
-  constexpr int kMtN = 4;  // traced iterations
-  unsigned long long* mtbuf = nullptr;
-  const size_t mtwaves = (size_t)std::max(h->march_grid, h->wm_grid) * kMarchWaves;
-  if (mtpath && h->march && a.sm && h->qfree) {
-    HIP_TRY(dmalloc(&mtbuf, (size_t)2 * kMtN * 4 * mtwaves));
-    HIP_TRY(hipMemsetAsync(mtbuf, 0, (size_t)2 * kMtN * 4 * mtwaves * 8, st));
-  }
-  while (true) {
-    for (int j = 0; j < chunk; ++j) {
-      const bool tm = T.enabled && j % kTimeEvery == 0;
-      hipEvent_t* ev = tm ? &T.ev[kEv * j] : nullptr;
-      a.kiter = (int)(launched + j + 1);
-      front_rows(h, front, a);
-      // (tag: exact in a double while solve_epoch < 2^29)
-      a.mtag = (double)(((unsigned long long)h->solve_epoch << 24) | (unsigned long long)a.kiter);
-      const int mti = a.kiter - mt_it;
-      a.mtrace = mtbuf && mti >= 0 && mti < kMtN ? mtbuf + (size_t)2 * mti * 4 * mtwaves : nullptr;
-      if (!h->fused) {
-        if (tm) h->ev_next[0] = ev[0], h->ev_next[1] = ev[1];
-        if (ST) klaunch(h, k_cg_p<true>, G, kBlock, st, a);
-        else klaunch(h, k_cg_p<false>, G, kBlock, st, a);
-        HIP_TRY(dbg_sync(st, "k_cg_p"));
-      }
-      if (tm) h->ev_next[0] = ev[2], h->ev_next[1] = ev[3];
-      HIP_TRY(launch_cg_spmv(h, a, G));
-      HIP_TRY(dbg_sync(st, "k_cg_spmv"));
-      if (host_fold) {  // akden in ascending j, then ak (on the host)
-        HIP_TRY(host_fold_qp(h, a, hf));
-      } else if (literal) {  // akden in ascending j, then ak
-        k_fold_qp<<<1, 64, 0, st>>>(a);
-        HIP_TRY(dbg_sync(st, "k_fold_qp"));
-      }
-      if (tm) h->ev_next[0] = ev[4], h->ev_next[1] = ev[5];
-      if (a.mtrace) a.mtrace += 4 * mtwaves;
-      HIP_TRY(launch_cg_b(h, a, G));
-      a.mtrace = nullptr;
-      HIP_TRY(dbg_sync(st, "k_cg_b"));
-      h->ev_next[0] = h->ev_next[1] = nullptr;
-      if (host_fold) {  // z.r and r.r in ascending j: bk, err, the stop test (host)
-        HIP_TRY(host_fold_b(h, a, hf));
-      } else if (literal) {  // z.r and r.r in ascending j: bk, err, the stop test
-        if (ST) k_fold_b<true><<<1, 64, 0, st>>>(a);
-        else k_fold_b<false><<<1, 64, 0, st>>>(a);
-        HIP_TRY(dbg_sync(st, "k_fold_b"));
-      }
-    }
-    launched += chunk;
-    e = hipGetLastError();
-    if (e != hipSuccess) break;
-    e = hipMemcpyAsync(hsp, d.scal, sizeof(CGScalars), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) break;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) break;
-    if (T.enabled) {  // launches of this chunk that did work
-      const int real = std::min(chunk, hsp->iter - done_iters);
-      int nt = 0;
-      for (int j = 0; j < real; j += kTimeEvery, ++nt) {
-        float tp = 0.f, ts = 0.f, tb = 0.f;
-        if (!h->fused) hipEventElapsedTime(&tp, T.ev[kEv * j], T.ev[kEv * j + 1]);
-        hipEventElapsedTime(&ts, T.ev[kEv * j + 2], T.ev[kEv * j + 3]);
-        hipEventElapsedTime(&tb, T.ev[kEv * j + 4], T.ev[kEv * j + 5]);
-        T.p_ms += tp;
-        T.spmv_ms += ts;
-        T.update_ms += tb;
-      }
-      T.spmv_n += nt;
-      T.update_n += nt;
-      T.p_n += nt;
-    }
-    done_iters = hsp->iter;
-    if (hsp->done) break;
-    // the first chunk walked every band; its read-back brings the source rows
-    if (front.on && launched == kFirstChunk && hsp->rhi >= hsp->rlo) {
-      front.lo = hsp->rlo / a.T.m;
-      front.hi = hsp->rhi / a.T.m;
-      front.known = front.hi < a.T.nrows;
-    }
-    if (launched > (long long)itmax + 2) break;  // cannot happen: device stops at itmax+1
-    chunk = std::min(chunk * 2, kMaxChunk);
-  }
-  if (e == hipSuccess && hsp->iter > 0 && !a.bx) {
-    k_cg_xfinal<<<G, kBlock, 0, st>>>(a);
-    e = dbg_sync(st, "k_cg_xfinal");
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  if (e == hipSuccess && hsp->iter > 0 && a.mxin) {  // the last B's x update
-    k_march_xpend<<<cdiv(2 * h->g.m, kBlock), kBlock, 0, st>>>(a);
-    e = dbg_sync(st, "k_march_xpend");
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  if (mtbuf) {
-    std::vector<unsigned long long> tr((size_t)2 * kMtN * 4 * mtwaves);
-    if (e == hipSuccess) e = hipMemcpy(tr.data(), mtbuf, tr.size() * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(mtbuf);
-    if (FILE* fo = e == hipSuccess ? fopen(mtpath, "a") : nullptr) {
-      fprintf(fo, "# m=%d nrows=%d band_rows=%d grid=%d waves=%zu (wall clock ticks, 100 MHz)\n"
-                  "iter,kernel,wave,t_entry,t_walk_end,t_exit,xcc,hw_id\n",
-              h->g.m, h->g.n - 2, h->march_h, h->march_grid, mtwaves);
-      for (int it = 0; it < kMtN; ++it)
-        for (int kb = 0; kb < 2; ++kb)
-          for (size_t wv = 0; wv < mtwaves; ++wv) {
-            const unsigned long long* v = &tr[((size_t)(2 * it + kb) * mtwaves + wv) * 4];
-            fprintf(fo, "%d,%s,%zu,%llu,%llu,%llu,%llu,%llu\n", mt_it + it, kb ? "B" : "P", wv, v[0],
-                    v[1], v[2], v[3] >> 32, v[3] & 0xffffffffull);
-          }
-      fclose(fo);
-    }
-  }
-  if (e == hipSuccess && a.mgran && hsp->pad[1] != 0) {
-    fprintf(stderr, "[perc] k_cg_march: reduction granule not seen within the poll limit\n");
-    e = hipErrorLaunchTimeOut;
-  }
-  *iter = hsp->iter;
-  *err = hsp->err;
-  // iterations that ran with a dead band (the launches past the stop did nothing)
-  h->last_front = std::max(0, std::min(hsp->iter, front.last_dead) - kFirstChunk);
-  hipHostFree(hsp);
-  return e;
+  HIP_TRY(solve_prologue(h, a, itol, x0_zero));
+  h->last_kernel = h->plan.family();
+  bool done = false;
+  HIP_TRY(solve_one_kernel(h, a, iter, err, &done));
+  if (done) return hipSuccess;
+  return solve_launched(h, a, itmax, x0_zero, iter, err);
 }
 }  // namespace
 
 hipError_t dev_spmv(perc_ctx* h, const double* x, double* y) {
-  if (!h->stencil) HIP_TRY(ensure_csr(h));
+  if (!h->plan.stencil) HIP_TRY(ensure_csr(h));
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
   const size_t bytes = sizeof(double) * h->N;
@@ -1466,7 +1431,7 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
   DeviceBuffers& d = h->d;
   hipStream_t st = h->stream;
   CGArgs a = make_cg_args(h);
-  const bool ST = h->stencil;
+  const bool ST = h->plan.stencil;
   // scalars for a steady-state iteration (iter = 1 -> general p update)
   CGScalars hs{};
   hs.bknum = 1.0;
@@ -1486,11 +1451,11 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
                          st));
   if (which == 6 && h->res_G <= 0) return hipErrorInvalidConfiguration;  // no resident grid
   // STREAM copy: 512 MB -> 512 MB, well past the 256 MB Infinity Cache
-  double *cp_src = nullptr, *cp_dst = nullptr;
+  DevBuf<double> cp_src, cp_dst;
   const size_t cp_n = (size_t)64 << 20;
   if (which == 4) {
-    HIP_TRY(dmalloc(&cp_src, cp_n));
-    HIP_TRY(dmalloc(&cp_dst, cp_n));
+    HIP_TRY(cp_src.alloc(cp_n));
+    HIP_TRY(cp_dst.alloc(cp_n));
     HIP_TRY(hipMemsetAsync(cp_src, 0, cp_n * sizeof(double), st));
   }
   hipError_t lerr = hipSuccess;
@@ -1523,14 +1488,14 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
       // a refused grid (CUs taken) must not time an empty stream
       keep(hipLaunchCooperativeKernel((const void*)k_res_sync_probe, dim3(ra.G), dim3(h->res_NT), args, 0, st));
     } else if (which == 5) {  // one whole iteration
-      if (!h->fused) {
+      if (!h->plan.fused) {
         if (ST) k_cg_p<true><<<G, kBlock, 0, st>>>(a);
         else k_cg_p<false><<<G, kBlock, 0, st>>>(a);
       }
       keep(launch_cg_spmv(h, a, G));
       keep(launch_cg_b(h, a, G));
     } else {
-      k_copy<<<cdiv(cp_n / 2, kBlock), kBlock, 0, st>>>(cp_src, cp_dst, (int)cp_n);
+      k_copy<<<cdiv(cp_n / 2, kBlock), kBlock, 0, st>>>(cp_src.get(), cp_dst.get(), (int)cp_n);
     }
   };
   // the B kernel advances iter (tol < 0 keeps it running); values are
@@ -1546,8 +1511,6 @@ hipError_t dev_bench(perc_ctx* h, int which, int reps, double* ms) {
   float t = 0.f;
   HIP_TRY(hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
   *ms = (double)t / reps / (which == 6 ? 16 : 1);
-  if (cp_src) HIP_TRY(hipFree(cp_src));
-  if (cp_dst) HIP_TRY(hipFree(cp_dst));
   return hipSuccess;
 }
 
